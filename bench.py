@@ -19,12 +19,21 @@ Default workload: BASELINE config 4 (512 UAVs, 4096 x 4096 = 16.8M-cell grid, K 
 the configuration the north-star targets are quoted on and the one the 1/2/4/8-GPU scaling
 run uses. `--config 2|3` selects the other synthetic configs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the poll
-chain and its dominant kernel, timed by in-kernel workgroup stamps (s_memrealtime: first
-workgroup start to last workgroup end of every launch, over the timed steps), and
-`cpu_baseline` = the oracle's C restatement of the reference loop (rank 0, N=1).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (the milliseconds one timed step took) and the workload's description. A plain run
+does only that: set-up, the warmup steps, the timed steps, the line. `--dump-outputs DIR` also
+writes what the last timed step returned to its caller as DIR/<name>.npy (float64; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output).
+
+`--full` adds everything else the benchmark measures or checks, each in runs of its own after
+the timed region: `roofline` for the poll chain and its dominant kernel, timed by in-kernel
+workgroup stamps (s_memrealtime: first workgroup start to last workgroup end of every launch),
+the parity guard of the timed poll against the streaming scan, the single-candidate closure and
+host-pointer poll timings, and `cpu_baseline` = the oracle's C restatement of the reference
+loop (rank 0, N=1). `--no-cpu` and `--no-extras` trim a `--full` run.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 4] [--algo auto]
+                    [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -48,6 +57,14 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s HBM3E (spec)
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array the last timed step returned."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"),
+                np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
 
 
 def cpu_model() -> str:
@@ -230,7 +247,8 @@ def stamp_setup(ctx, stamp_timed):
     off until the stamped pass after the timed region. Ranks sharing one GPU (the gloo rehearsals) ran the
     config-5 loop at 35.6 ms per MPC step with this set-up first done after the timed region, 22.6-24.4
     with it before (same box; cause not identified; single-GPU runs: profiles/r06_stamp_setup_ab.json).
-    MAXCOVER_BENCH_NO_STAMP_SETUP=1 skips it (for that A/B)."""
+    MAXCOVER_BENCH_NO_STAMP_SETUP=1 skips it (for that A/B). A plain run (no --full) reads no stamp
+    but keeps this set-up, so that its timed region starts from the state a --full run's does."""
     if stamp_timed or os.environ.get("MAXCOVER_BENCH_NO_STAMP_SETUP") != "1":
         ctx.profile(True)
         ctx.profile_read(reset=True)
@@ -371,16 +389,21 @@ def bench_config5(args, pkg, dev_index, rank=0, world=1, coll_dev=None):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    if not stamp_timed:
+    full = args.full
+    if args.dump_outputs and rank == 0:
+        # what the last timed MPC step handed its caller: the MADS run's iterate and objective
+        dump_outputs(args.dump_outputs, {"circles": sim.outputs[-1], "objective": [recs[-1]["f"]]})
+    if full and not stamp_timed:
         ctx.profile(True)
         ctx.profile_read(reset=True)
         for _ in range(args.steps):
             sim.step()
         torch.cuda.synchronize()
-    split = ctx.profile_split()
-    kern = ctx.profile_kernels()
-    k_ms, k_launches, k_cands, k_walk = ctx.profile_read(reset=True)
-    ctx.profile(False)
+    if full:
+        split = ctx.profile_split()
+        kern = ctx.profile_kernels()
+        k_ms, k_launches, k_cands, k_walk = ctx.profile_read(reset=True)
+        ctx.profile(False)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -420,22 +443,44 @@ def bench_config5(args, pkg, dev_index, rank=0, world=1, coll_dev=None):
     iters = sum(r["iterations"] for r in recs)
     succ = sum(r["successes"] for r in recs)
     M_avg = float(np.mean([r["points"] for r in recs]))
-    b_eval = 24 * M_avg + 24 * cfg["N"] + 8
-    avg_launch_ms = k_ms / max(k_launches, 1)
-    cands_per_launch = k_cands / max(k_launches, 1)
-    # roofline as config 4's: the byte floor of one exact culling poll — here a
-    # representative one, the LTMADS poll (l = 2) around the final incumbent on the final point
-    # list; the generated poll reads only the incumbent and the permutations (no matrix) — over
-    # the mean device chain per poll (in-kernel stamps)
-    kernels, dominant = kernel_table(kern)
-    x, y, w = ctx.get_points()
-    polls = wl.poll_candidates(sim.x_prev, wl.SplitMix64(args.seed + 1))
-    n = polls.shape[1]
-    floor = floor_bytes_points(x, y, w, polls, 8 * n + 2 * 4 * n)
-    chain_ms = (split[0] + split[1] + split[2]) / split[3] if split[3] else None
-    achieved = floor["bytes"] / (chain_ms * 1e-3) / 1e9 if chain_ms else None
-    cpu = None
-    if not args.no_cpu and world == 1:
+    roofline = cpu = None
+    if full:
+        b_eval = 24 * M_avg + 24 * cfg["N"] + 8
+        avg_launch_ms = k_ms / max(k_launches, 1)
+        cands_per_launch = k_cands / max(k_launches, 1)
+        # roofline as config 4's: the byte floor of one exact culling poll — here a
+        # representative one, the LTMADS poll (l = 2) around the final incumbent on the final point
+        # list; the generated poll reads only the incumbent and the permutations (no matrix) — over
+        # the mean device chain per poll (in-kernel stamps)
+        kernels, dominant = kernel_table(kern)
+        x, y, w = ctx.get_points()
+        polls = wl.poll_candidates(sim.x_prev, wl.SplitMix64(args.seed + 1))
+        n = polls.shape[1]
+        floor = floor_bytes_points(x, y, w, polls, 8 * n + 2 * 4 * n)
+        chain_ms = (split[0] + split[1] + split[2]) / split[3] if split[3] else None
+        achieved = floor["bytes"] / (chain_ms * 1e-3) / 1e9 if chain_ms else None
+        roofline = {
+            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": None,
+            "kernel": (f"poll chains ({', '.join(k for k, v in kernels.items() if v.get('launches'))}); "
+                       f"dominant kernel {dominant}"),
+            "chain_ms": chain_ms, "polls": split[3],
+            "split_ms_per_poll": ({"prep": split[0] / split[3], "walk": split[1] / split[3],
+                                   "after_walk": split[2] / split[3]} if split[3] else None),
+            "floor": floor, "evals_per_launch": cands_per_launch,
+            "dominant_kernel": dominant,
+            "avg_launch_ms": kernels[dominant]["avg_us"] * 1e-3 if dominant else avg_launch_ms,
+            "kernels": kernels,
+            "brute_force_equiv": {"bytes_per_eval": b_eval,
+                                  "note": "SURVEY 8(d)'s full-scan bytes per evaluation at the mean "
+                                          "list length: not a roofline of this algorithm"},
+            "note": "achieved = floor.bytes (a representative poll: the final incumbent's) / the "
+                    "mean device chain per poll (first workgroup start of its first launch to the "
+                    "last workgroup end of finalize, in-kernel stamps)",
+            "timing": ("in-kernel stamps over the timed MPC steps" if args.stamps == "timed" else
+                       f"in-kernel stamps over {args.steps} MPC steps run right after the timed ones"),
+        }
+    if full and not args.no_cpu and world == 1:
         threads, cinfo = usable_cpus()
         try:
             # the CPU sample evaluates what the reference would: the candidates passing cons3
@@ -456,7 +501,7 @@ def bench_config5(args, pkg, dev_index, rank=0, world=1, coll_dev=None):
         "metric": METRIC, "value": feas / elapsed, "unit": "evals/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic (seeded CA fire)",
+        "data": "synthetic (seeded CA fire)", "full": full,
         "config": {
             "workload": f"config 5: {cfg['name']}", "uavs": cfg["N"],
             "fire_grid": f"{cfg['G']}x{cfg['G']} cells @ 5 m, ignition {cfg['ignition']}^2 cells",
@@ -493,27 +538,7 @@ def bench_config5(args, pkg, dev_index, rank=0, world=1, coll_dev=None):
                             f"per MADS iteration; fire stream regenerated per GPU"),
             "ranks_in_lockstep": lockstep,
         },
-        "roofline": {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": None,
-            "kernel": (f"poll chains ({', '.join(k for k, v in kernels.items() if v.get('launches'))}); "
-                       f"dominant kernel {dominant}"),
-            "chain_ms": chain_ms, "polls": split[3],
-            "split_ms_per_poll": ({"prep": split[0] / split[3], "walk": split[1] / split[3],
-                                   "after_walk": split[2] / split[3]} if split[3] else None),
-            "floor": floor, "evals_per_launch": cands_per_launch,
-            "dominant_kernel": dominant,
-            "avg_launch_ms": kernels[dominant]["avg_us"] * 1e-3 if dominant else avg_launch_ms,
-            "kernels": kernels,
-            "brute_force_equiv": {"bytes_per_eval": b_eval,
-                                  "note": "SURVEY 8(d)'s full-scan bytes per evaluation at the mean "
-                                          "list length: not a roofline of this algorithm"},
-            "note": "achieved = floor.bytes (a representative poll: the final incumbent's) / the "
-                    "mean device chain per poll (first workgroup start of its first launch to the "
-                    "last workgroup end of finalize, in-kernel stamps)",
-            "timing": ("in-kernel stamps over the timed MPC steps" if args.stamps == "timed" else
-                       f"in-kernel stamps over {args.steps} MPC steps run right after the timed ones"),
-        },
+        "roofline": roofline,
         "cpu_baseline": cpu,
         "setup_s": t_set,
     }
@@ -550,11 +575,21 @@ def main():
                          "256-MB Infinity Cache holds, so every poll reads its matrix from HBM)")
     ap.add_argument("--tile-points", type=int, default=None,
                     help="points per spatial tile of the index (library default when omitted)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures "
+                         "or checks: the stamped pass (roofline, per-kernel times), the parity "
+                         "guard, the closure and host-poll timings, the CPU baseline. Off by "
+                         "default: a plain run sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64): best.npy = (objective, candidate index) of the poll (configs "
+                         "2-4); circles.npy and objective.npy = the MADS run's iterate and its "
+                         "objective (config 5). Written by rank 0")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the parity guard and the closure timing (profiler passes: only "
-                         "the warmup and timed polls launch kernels after set-up)")
+                    help="--full without the parity guard and the closure timing (profiler passes: "
+                         "only the warmup, timed and stamped polls launch kernels after set-up)")
     ap.add_argument("--seed", type=int, default=20250216)
     ap.add_argument("--scaling", default="weak", choices=("strong", "weak"),
                     help="N>1: weak (default) = one full poll set per GPU (P*K candidates per "
@@ -591,6 +626,12 @@ def main():
                     help="nccl (= RCCL on ROCm) for the real multi-GPU run; gloo only to rehearse "
                          "N>1 with several ranks sharing one GPU (MAXCOVER_BENCH_DEVICE)")
     args = ap.parse_args()
+    if args.stamps == "timed" and not args.full:
+        ap.error("--stamps timed reads the in-kernel stamps, which only --full reports")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.steps is None:
         args.steps = 3 if args.config == 5 else 200
     if args.warmup is None:
@@ -801,17 +842,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    if not stamp_timed:   # the stamped pass: the same polls (the same poll sets, in order)
+    full = args.full
+    if full and not stamp_timed:   # the stamped pass: the same polls (the same poll sets, in order)
         ctx.profile(True)
         ctx.profile_read(reset=True)
         if armed:
             arm(args.warmup % nb)
         run_steps(args.warmup)
         torch.cuda.synchronize(dev)
-    split = ctx.profile_split()
-    kern = ctx.profile_kernels()
-    k_ms, k_launches, k_cands, k_walk = ctx.profile_read(reset=True)
-    ctx.profile(False)
+    if full:
+        split = ctx.profile_split()
+        kern = ctx.profile_kernels()
+        k_ms, k_launches, k_cands, k_walk = ctx.profile_read(reset=True)
+        ctx.profile(False)
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -819,12 +862,15 @@ def main():
     if result is None:
         b = d_best.cpu()
         result = (float(b[0]), int(b.view(torch.int64)[1]))
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the poll's best (objective, global index)
+        dump_outputs(args.dump_outputs, {"best": [result[0], result[1]]})
 
     # (after the timed region, which follows the warmup directly) correctness guard on the timed workload: the timed poll (this rank's shard, the device's
     # walk choice, cons3) writes every objective; 16 sampled candidates plus its argmin are
     # re-evaluated by the streaming scan (an independent kernel) and must agree bit for bit
     check = None
-    if K > 1 and not args.no_extras:
+    if full and K > 1 and not args.no_extras:
         d_obj = torch.empty(Kl, dtype=torch.float64, device=dev)
         ctx.poll_best_dev(d_polls[0], 3 * N, Kl, d_rmax, d_best, d_prev=d_prevs[0], d_dlim=d_dlim,
                           tan_half_fov=tan_half, idx_base=idx_base, d_obj=d_obj, stream=s_handle)
@@ -853,22 +899,68 @@ def main():
     # over the timed steps. Its algorithmic floor is what any exact culling evaluation must move:
     # the candidate matrix read once, every entry that lies in some disk's poll-wide footprint
     # box read once (xy, 16 B; w only when the weights differ), and the 16-B result.
-    avg_launch_ms = k_ms / max(k_launches, 1)
-    cands_per_launch = k_cands / max(k_launches, 1)
-    floor = floor_bytes(x, y, w, polls[0][lo:hi], G)
-    # the unit is the whole poll chain on the device: first workgroup start of its first launch
-    # to the last workgroup end of its last (finalize + argmin), from the in-kernel stamps
-    chain_ms = (split[0] + split[1] + split[2]) / split[3] if split[3] else None
-    unit_ms = chain_ms if chain_ms else avg_launch_ms
-    achieved = floor["bytes"] / (unit_ms * 1e-3) / 1e9 if (k_launches and unit_ms) else None
-    b_eval = 3 * M * 8 + 3 * N * 8 + 8     # a brute-force scan per candidate
-    traffic, traffic_src, pmc_per = pmc_traffic(args.config, args.disks, world, args.algo)
-    kernels, dominant = kernel_table(kern, pmc_per)
+    roofline = None
+    if full:
+        avg_launch_ms = k_ms / max(k_launches, 1)
+        cands_per_launch = k_cands / max(k_launches, 1)
+        floor = floor_bytes(x, y, w, polls[0][lo:hi], G)
+        # the unit is the whole poll chain on the device: first workgroup start of its first launch
+        # to the last workgroup end of its last (finalize + argmin), from the in-kernel stamps
+        chain_ms = (split[0] + split[1] + split[2]) / split[3] if split[3] else None
+        unit_ms = chain_ms if chain_ms else avg_launch_ms
+        achieved = floor["bytes"] / (unit_ms * 1e-3) / 1e9 if (k_launches and unit_ms) else None
+        b_eval = 3 * M * 8 + 3 * N * 8 + 8     # a brute-force scan per candidate
+        traffic, traffic_src, pmc_per = pmc_traffic(args.config, args.disks, world, args.algo)
+        kernels, dominant = kernel_table(kern, pmc_per)
+        roofline = {
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+            "traffic": traffic,
+            "kernel": (f"poll chain ({', '.join(k for k, v in kernels.items() if v.get('launches'))}); "
+                       f"dominant kernel {dominant}"),
+            "chain_ms": chain_ms,
+            "dominant_kernel": dominant,
+            "dominant_basis": ("in-kernel stamps: first workgroup start to last workgroup end; "
+                               "rocprof's dispatch-to-completion durations add the dispatch "
+                               "ramp and the end-of-kernel release, which weigh most on the "
+                               "prep launch (512 x 512-thread workgroups, 10 MB of stores), "
+                               "and can rank it first (profiles/*rocprof*config4.csv)"),
+            "avg_launch_ms": (kernels[dominant]["avg_us"] * 1e-3 if dominant else avg_launch_ms),
+            "kernels": kernels,
+            "walk_avg_launch_ms": avg_launch_ms,
+            "evals_per_launch": cands_per_launch,
+            "split_ms_per_poll": ({"prep": split[0] / split[3], "walk": split[1] / split[3],
+                                   "after_walk": split[2] / split[3]} if split[3] else None),
+            "floor": floor,
+            "traffic_source": traffic_src,
+            "traffic_frac": (traffic / (unit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                             if traffic and unit_ms else None),
+            "brute_force_equiv": {
+                "bytes_per_eval": b_eval,
+                "achieved": b_eval * cands_per_launch / (avg_launch_ms * 1e-3) / 1e9
+                if k_launches else None,
+                "note": "SURVEY 8(d)'s full-scan bytes per evaluation: what a brute-force "
+                        "scan would have to stream, not a roofline of this algorithm"},
+            "timing": ("in-kernel workgroup stamps (s_memrealtime) over the timed steps"
+                       if args.stamps == "timed" else
+                       "in-kernel workgroup stamps (s_memrealtime) over a second pass of the "
+                       "timed steps (the same polls), run right after the timed region"),
+            "note": "achieved = floor.bytes / chain_ms (first workgroup start of the chain's "
+                    "first launch to the last workgroup end of its last); avg_launch_ms = the "
+                    "dominant (longest) kernel alone, kernels = every launch of the chain "
+                    "(in-kernel stamps over the timed steps; compare with profiles/*rocprof*); "
+                    "traffic = PMC-measured HBM bytes of the whole chain per poll (per kernel "
+                    "in kernels.*.hbm_bytes), attached only when the kernel sources hash to "
+                    "the profiled build",
+        }
 
     # the single-candidate closure path (src/TDM_STATIC_opt.jl:125: DirectSearch calls the
     # objective once per trial point): host-pointer mac_area_f64 latency on the timed workload
     closure = None
-    if rank == 0 and not args.no_extras:
+    if full and rank == 0 and not args.no_extras:
         c0 = np.ascontiguousarray(polls[0][min(1, K - 1)])
         for _ in range(20):
             ctx.area(c0)
@@ -886,7 +978,7 @@ def main():
     # the basis form (mac_poll_best_basis: incumbent + L's packed triangle + permutations + delta,
     # mac_poll_basis_f64), both with cons3, timed per call on the same poll (results must agree)
     host_poll = None
-    if rank == 0 and not args.no_extras and K > 1 and args.disk_shard_of == 1:
+    if full and rank == 0 and not args.no_extras and K > 1 and args.disk_shard_of == 1:
         n = 3 * N
         Lm, rp_, cp_ = wl.ltmads_basis_parts(n, 2, wl.SplitMix64(args.seed + 11))
         Bm = Lm[rp_][:, cp_].astype(np.float64)
@@ -916,7 +1008,7 @@ def main():
     out = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu and world == 1:
+        if full and not args.no_cpu and world == 1:
             threads, cinfo = usable_cpus()
             try:
                 v, desc = cpu_baseline(x, y, w, polls[0], args.cpu_seconds, threads)
@@ -937,6 +1029,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
+            "full": full,
             "config": {
                 "workload": f"config {args.config}: {cfg['name']}",
                 "uavs": N, "cells": M, "grid": f"{G}x{G} @ 5 m", "candidates_per_poll": K,
@@ -959,50 +1052,7 @@ def main():
                 "poll_sets": args.polls,
                 "poll_sets_bytes": int(args.polls * K * 3 * N * 8),
             },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                "traffic": traffic,
-                "kernel": (f"poll chain ({', '.join(k for k, v in kernels.items() if v.get('launches'))}); "
-                           f"dominant kernel {dominant}"),
-                "chain_ms": chain_ms,
-                "dominant_kernel": dominant,
-                "dominant_basis": ("in-kernel stamps: first workgroup start to last workgroup end; "
-                                   "rocprof's dispatch-to-completion durations add the dispatch "
-                                   "ramp and the end-of-kernel release, which weigh most on the "
-                                   "prep launch (512 x 512-thread workgroups, 10 MB of stores), "
-                                   "and can rank it first (profiles/*rocprof*config4.csv)"),
-                "avg_launch_ms": (kernels[dominant]["avg_us"] * 1e-3 if dominant else avg_launch_ms),
-                "kernels": kernels,
-                "walk_avg_launch_ms": avg_launch_ms,
-                "evals_per_launch": cands_per_launch,
-                "split_ms_per_poll": ({"prep": split[0] / split[3], "walk": split[1] / split[3],
-                                       "after_walk": split[2] / split[3]} if split[3] else None),
-                "floor": floor,
-                "traffic_source": traffic_src,
-                "traffic_frac": (traffic / (unit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-                                 if traffic and unit_ms else None),
-                "brute_force_equiv": {
-                    "bytes_per_eval": b_eval,
-                    "achieved": b_eval * cands_per_launch / (avg_launch_ms * 1e-3) / 1e9
-                    if k_launches else None,
-                    "note": "SURVEY 8(d)'s full-scan bytes per evaluation: what a brute-force "
-                            "scan would have to stream, not a roofline of this algorithm"},
-                "timing": ("in-kernel workgroup stamps (s_memrealtime) over the timed steps"
-                           if args.stamps == "timed" else
-                           "in-kernel workgroup stamps (s_memrealtime) over a second pass of the "
-                           "timed steps (the same polls), run right after the timed region"),
-                "note": "achieved = floor.bytes / chain_ms (first workgroup start of the chain's "
-                        "first launch to the last workgroup end of its last); avg_launch_ms = the "
-                        "dominant (longest) kernel alone, kernels = every launch of the chain "
-                        "(in-kernel stamps over the timed steps; compare with profiles/*rocprof*); "
-                        "traffic = PMC-measured HBM bytes of the whole chain per poll (per kernel "
-                        "in kernels.*.hbm_bytes), attached only when the kernel sources hash to "
-                        "the profiled build",
-            },
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "closure": closure,
             "host_poll_ms": host_poll,

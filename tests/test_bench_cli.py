@@ -52,6 +52,27 @@ def test_mismatched_world_exits_nonzero(ws, gpus):
     assert not r.stdout.strip()   # no JSON line
 
 
+@pytest.mark.parametrize("argv", [["--stamps", "timed"], ["--full", "--steps", "0"],
+                                  ["--warmup", "-1"]])
+def test_bad_arguments_exit_before_any_gpu_work(argv):
+    """The in-kernel stamps are read only under --full, and --steps sets the number of timed
+    steps (ms_per_step divides by it), so neither is accepted where it could not be honoured."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *argv],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2
+    assert not r.stdout.strip()
+
+
+def test_dump_outputs_are_float64_npy(tmp_path):
+    import numpy as np
+    d = tmp_path / "a" / "b"   # created on demand
+    bench.dump_outputs(str(d), {"best": [1.5, 7], "circles": np.arange(6, dtype=np.float32)})
+    best, circles = np.load(d / "best.npy"), np.load(d / "circles.npy")
+    assert best.dtype == circles.dtype == np.float64
+    assert best.tolist() == [1.5, 7.0] and circles.tolist() == [0, 1, 2, 3, 4, 5]
+    assert sorted(p.name for p in d.iterdir()) == ["best.npy", "circles.npy"]
+
+
 def test_gpus_beyond_visible_devices_exits_nonzero():
     """--gpus 2 with no launcher on a host without 2 GPUs (this container has none): the
     launcher is not started and the exit status is non-zero (no 1-GPU line passes for 2)."""

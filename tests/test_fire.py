@@ -66,10 +66,11 @@ def test_firepoints_converter_roundtrip(pkg, firepoints, tmp_path):
     assert back[len(firepoints)].shape == (0, 5)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/src/FirePoints.xlsx"),
-                    reason="reference data not present (build container only)")
 def test_firepoints_xlsx_reader_matches_fixture(pkg, firepoints):
-    rows = pkg.firepoints.read_xlsx("/root/reference/src/FirePoints.xlsx")
+    """tests/golden/FirePoints.xlsx is the reference's own table (src/FirePoints.xlsx, data only),
+    firepoints.csv its conversion (tests/golden/make_golden.py)."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    rows = pkg.firepoints.read_xlsx(os.path.join(here, "golden", "FirePoints.xlsx"))
     assert len(rows) == len(firepoints) == 68
     assert all(np.array_equal(a, b) for a, b in zip(rows, firepoints))
 

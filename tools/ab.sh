@@ -3,14 +3,15 @@
 # bench.py (no CPU baseline, no extras) and prints each run's chain and ms per poll.
 # Usage: tools/ab.sh path/to/libA.so path/to/libB.so [rounds]
 set -u
+OUT=${OUT:-bench_out}   # where the logs go
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/ab
+mkdir -p $OUT/ab
 A=$1; B=$2; R=${3:-3}
 for r in $(seq 1 "$R"); do
   for v in A B; do
     lib=$A; [ "$v" = B ] && lib=$B
-    MAXCOVER_LIB=$lib timeout -k 10 120 python bench.py --no-cpu --no-extras --steps 40 > gpurun_out/ab/$v$r.log 2>&1 || exit $?
-    python3 - "$v" "gpurun_out/ab/$v$r.log" <<'PY'
+    MAXCOVER_LIB=$lib timeout -k 10 120 python bench.py --full --no-cpu --no-extras --steps 40 > $OUT/ab/$v$r.log 2>&1 || exit $?
+    python3 - "$v" "$OUT/ab/$v$r.log" <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[2]) if l.startswith("{")][0]
 d = json.loads(line)

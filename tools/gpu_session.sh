@@ -43,15 +43,15 @@ for s in $STEPS; do
     smoke)
         run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ; rc=$? ;;
     benchq)
-        run benchq 300 python bench.py --no-cpu ; rc=$? ;;
+        run benchq 300 python bench.py --full --no-cpu ; rc=$? ;;
     benchplain)   # config 4, polls launched one after another (no doorbell)
-        run benchplain 300 python bench.py --no-cpu --step-mode plain ; rc=$? ;;
+        run benchplain 300 python bench.py --full --no-cpu --step-mode plain ; rc=$? ;;
     bench)
-        run bench 400 python bench.py ; rc=$?
+        run bench 400 python bench.py --full ; rc=$?
         grep '^{' gpurun_out/bench.log > gpurun_out/bench_${TAG}.json ;;
     algos)
         for a in tiled poll auto; do
-            run bench_$a 600 python bench.py --no-cpu --algo $a --steps 30 ; rc=$?
+            run bench_$a 600 python bench.py --full --no-cpu --algo $a --steps 30 ; rc=$?
             fatal $rc && break
         done ;;
     diag)
@@ -72,10 +72,10 @@ for s in $STEPS; do
             run diagidx 600 python tools/diag_index.py ; rc=$? ;;
     weak2)   # rehearsal of the N=2 path on one GPU (gloo; both ranks on device 0)
         MAXCOVER_BENCH_DEVICE=0 run weak2 300 python -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 \
+            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 \
             --no-cpu --dist-backend gloo --steps 20 ; rc=$? ;;
     self2)   # bench.py --gpus 2 with no external launcher: it starts its two ranks itself (gloo; both on device 0)
-        MAXCOVER_BENCH_DEVICE=0 run self2 300 python bench.py --gpus 2 --no-cpu --dist-backend gloo --steps 20 ; rc=$?
+        MAXCOVER_BENCH_DEVICE=0 run self2 300 python bench.py --full --gpus 2 --no-cpu --dist-backend gloo --steps 20 ; rc=$?
         grep '^{' gpurun_out/self2.log > gpurun_out/self2_${TAG}.json ;;
     diagor)   # phase times of the union pass on the config-5 regression poll at ell 5 / 4 / 3
         MAXCOVER_LIB=$PWD/maximumareacoverageoptimization.jl_amd/libmaxcover_diag.so \
@@ -89,12 +89,12 @@ for s in $STEPS; do
         run c5polls 600 python tools/c5_polls.py ; rc=$? ;;
     c5x2)    # rehearsal of the N=2 config-5 path (sharded MADS) on one GPU (gloo; both ranks on device 0)
         MAXCOVER_BENCH_DEVICE=0 run c5x2 400 python -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 \
+            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 2 \
             --config 5 --no-cpu --dist-backend gloo --steps 2 --warmup 1 --mads-mode shard ; rc=$?
         grep '^{' gpurun_out/c5x2.log > gpurun_out/c5x2_${TAG}.json ;;
     c5x2s)   # the speculative N=2 config-5 loop on one GPU (gloo; both ranks on device 0)
         MAXCOVER_BENCH_DEVICE=0 run c5x2s 400 python -m torch.distributed.run --nnodes=1 \
-            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 \
+            --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --full --gpus 2 \
             --config 5 --no-cpu --dist-backend gloo --steps 2 --warmup 1 --mads-mode speculate ; rc=$?
         grep '^{' gpurun_out/c5x2s.log > gpurun_out/c5x2s_${TAG}.json ;;
     probe)
@@ -102,56 +102,56 @@ for s in $STEPS; do
           cat /sys/fs/cgroup/cpu.max 2>/dev/null; lscpu | grep -E 'Model name|Socket|Core|Thread'; 
           echo OMP=$OMP_NUM_THREADS; } > gpurun_out/probe.log 2>&1; cat gpurun_out/probe.log; rc=0 ;;
     benchc)
-        run benchc 400 python bench.py --disks clustered --no-cpu ; rc=$?
+        run benchc 400 python bench.py --full --disks clustered --no-cpu ; rc=$?
         grep '^{' gpurun_out/benchc.log > gpurun_out/benchc_${TAG}.json ;;
     bench3)
-        run bench3 600 python bench.py --config 3 --no-cpu ; rc=$? ;;
+        run bench3 600 python bench.py --full --config 3 --no-cpu ; rc=$? ;;
     chains5)   # config 5 through each forced chain
         for c in five fused; do
-            run bench5_$c 600 python bench.py --config 5 --steps 2 --warmup 1 --no-cpu --chain $c ; rc=$?
+            run bench5_$c 600 python bench.py --full --config 5 --steps 2 --warmup 1 --no-cpu --chain $c ; rc=$?
             fatal $rc && break
         done ;;
     chains4)   # config 4 through each forced chain
         for c in five fused; do
-            run bench4_$c 300 python bench.py --no-cpu --no-extras --chain $c ; rc=$?
+            run bench4_$c 300 python bench.py --full --no-cpu --no-extras --chain $c ; rc=$?
             fatal $rc && break
         done ;;
     bench5)
-        run bench5 600 python bench.py --config 5 --steps 3 --warmup 1 --no-cpu ; rc=$? ;;
+        run bench5 600 python bench.py --full --config 5 --steps 3 --warmup 1 --no-cpu ; rc=$? ;;
     shards)   # per-rank chain floor of the strong split: rank 0's shard alone on one GPU
         for P in 2 4 8; do
-            run shard$P 300 python bench.py --no-cpu --shard-of $P ; rc=$?
+            run shard$P 300 python bench.py --full --no-cpu --shard-of $P ; rc=$?
             fatal $rc && break
         done ;;
     dshards)   # per-rank floor of a disk split: rank 0's disks alone on one GPU
         for P in 2 4 8; do
-            run dshard$P 300 python bench.py --no-cpu --no-extras --disk-shard-of $P ; rc=$?
+            run dshard$P 300 python bench.py --full --no-cpu --no-extras --disk-shard-of $P ; rc=$?
             fatal $rc && break
         done ;;
     prof5)    # kernel stats of the config-5 MPC loop and of the clustered config-4 poll
         rm -rf gpurun_out/prof5 gpurun_out/profc
         run prof5 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof5 -o run \
-            -- python3 bench.py --config 5 --steps 2 --warmup 1 --no-cpu ; rc=$?
+            -- python3 bench.py --full --config 5 --steps 2 --warmup 1 --no-cpu ; rc=$?
         fatal $rc || run profc 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profc -o run \
-            -- python3 bench.py --disks clustered --steps 10 --warmup 2 --no-cpu --no-extras ; rc=$? ;;
+            -- python3 bench.py --full --disks clustered --steps 10 --warmup 2 --no-cpu --no-extras ; rc=$? ;;
     cprof)   # the single-candidate closure path: latency + kernel stats
         rm -rf gpurun_out/cprof
         run cprof 200 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/cprof -o run \
             -- python3 tools/closure_prof.py ; rc=$? ;;
     bench2)
-        run bench2 600 python bench.py --config 2 --no-cpu ; rc=$? ;;
+        run bench2 600 python bench.py --full --config 2 --no-cpu ; rc=$? ;;
     prof)
         rm -rf gpurun_out/prof
         run prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run \
-            -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-extras ; rc=$?
+            -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu --no-extras ; rc=$?
         find gpurun_out/prof -name '*stats*' | head ;;
     pmc)
         rm -rf gpurun_out/pmc_fetch gpurun_out/pmc_write
         run pmc_fetch 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -o run \
-            -- python3 bench.py --steps 5 --warmup 1 --no-cpu --no-extras ; rc=$?
+            -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-extras ; rc=$?
         if ! fatal $rc; then
             run pmc_write 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -o run \
-                -- python3 bench.py --steps 5 --warmup 1 --no-cpu --no-extras ; rc=$?
+                -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-extras ; rc=$?
         fi
         fatal $rc || python3 tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write --config 4 \
             --chain 'mac::prep_x_kernel<false>;mac::fiw_kernel<true>;mac::fin2_kernel<true>' \

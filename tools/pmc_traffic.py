@@ -15,8 +15,8 @@ kernels the corrected figure is an upper bound and the raw one a lower bound; bo
 per kernel and per poll). "hbm_bytes_per_poll" sums the kernels
 of one poll chain (--chain; the default launch chain by default), which bench.py reports as
 roofline.traffic — only while the library sources hash to "src_sha" (bench.src_hash), i.e. the
-build that was profiled. Run the passes with `bench.py --no-extras` so that only the poll chain
-launches after set-up.
+build that was profiled. Run the passes over a plain `bench.py` run or `bench.py --full --no-cpu
+--no-extras`, so that only the poll chain launches after set-up.
 """
 from __future__ import annotations
 
@@ -87,7 +87,7 @@ def main():
         "hbm_bytes_per_poll": sum(kernels[k]["hbm_bytes_per_launch"] for k in chain),
         "hbm_bytes_per_poll_raw": sum(kernels[k]["hbm_bytes_per_launch_raw"] for k in chain),
         "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over "
-                  "`python3 bench.py --steps 5 --warmup 1 --no-cpu --no-extras`; bytes = "
+                  "`python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-extras`; bytes = "
                   "2*FETCH_SIZE*1024 + WRITE_SIZE*1024 (gfx950 FETCH correction, "
                   "MI355X_MICROARCH.md: calibrated for wide streaming reads, so an upper bound "
                   "for gathers); *_raw = FETCH_SIZE*1024 + WRITE_SIZE*1024 (a lower bound)",
