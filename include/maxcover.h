@@ -137,6 +137,28 @@ int32_t mac_area_f64(mac_ctx* ctx, const double* circles, int64_t three_n, doubl
 /* K candidates, column-major 3N x K (each candidate contiguous, as a Julia Matrix(3N,K)). */
 int32_t mac_area_batch_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
                            double* area_out);
+/* Per-UAV attribution of a candidate's coverage (the credits the reference's first-hit `break`
+ * loop sums, src/AreaCoverageCalculation.jl:67-78, kept apart), one kernel launch:
+ *   owned[i]     = sum of w_p over entries whose first covering disk in index order is disk i
+ *                  (sum_i owned[i] is calculateArea);
+ *   exclusive[i] = sum of w_p over entries covered by disk i and by no other disk
+ *                  (= area(all disks) - area(all disks but i); exclusive[i] <= owned[i]);
+ *   area         = the union's covered weight, the value mac_area_f64 returns.
+ * A disk with r <= 0, a NaN radius or a NaN centre covers nothing: it owns nothing and takes
+ * nothing from another disk's exclusive part. Of two identical disks the lower index owns their
+ * common entries and neither is exclusive there. With equal weights every value is an entry count
+ * times the weight (exact; area bit-identical to mac_area_f64); otherwise an fp64 sum in a fixed,
+ * run-to-run reproducible order. Every output pointer is nullable, but at least one must be given.
+ * N <= 2048 (MAC_E_INVAL above); K = 0 writes nothing; three_n = 0 or an empty list gives zeros.
+ * Host calls may run concurrently with mac_area_* / mac_poll_* on one context (not overlapping a
+ * point-list change). fp64 callers only: there is no *_f32 form of these calls.
+ * One candidate: owned_out / exclusive_out N doubles, area_out one double. */
+int32_t mac_area_by_disk_f64(mac_ctx* ctx, const double* circles, int64_t three_n,
+                             double* owned_out, double* exclusive_out, double* area_out);
+/* K candidates, 3N x K column-major in; owned / exclusive N x K column-major out (candidate k's N
+ * values contiguous), area_out K doubles. */
+int32_t mac_area_by_disk_batch_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                                   double* owned_out, double* exclusive_out, double* area_out);
 /* AreaMaxObjective for K candidates: obj_k = -area_k + penalty * sum_i |x[2N+i] - r_max[i]|
  * (penalty = 1e5 in the reference). r_max: N doubles. */
 int32_t mac_objective_batch_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
@@ -273,6 +295,9 @@ int32_t mac_poll_best_f32(mac_ctx* ctx, const float* cands, int64_t three_n, int
  * after enqueueing. */
 int32_t mac_area_batch_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
                                double* d_area, void* stream);
+/* mac_area_by_disk_batch_f64 on device pointers, stream-ordered; returns after enqueueing. */
+int32_t mac_area_by_disk_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
+                                 double* d_owned, double* d_exclusive, double* d_area, void* stream);
 /* Device poll: d_best receives {best_obj (double), best_idx (int64 stored as double bits)}
  * as 16 bytes; d_obj (nullable) K objectives. d_prev/d_dlim nullable (no cons3). */
 int32_t mac_poll_best_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,

@@ -16,7 +16,7 @@ is what the parity tests exercise. See INTEGRATION.md.
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, mads_run
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
     joinpath(@__DIR__, "..", "maximumareacoverageoptimization.jl_amd", "libmaxcover.so"))
@@ -88,6 +88,23 @@ function calculateArea(circles::Vector{Float64}, ctx::MacContext)
     check(ccall((:mac_area_f64, libmaxcover), Int32,
                 (Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Float64}), ctx, circles, length(circles), out))
     return out[]
+end
+
+"""
+Per-UAV attribution against the context's resident point list: `(owned, exclusive, area)`.
+`owned[i]` is the weight of the entries whose first covering disk in index order is disk i
+(`sum(owned) == calculateArea`), `exclusive[i]` the weight disk i alone covers.
+"""
+function area_by_disk(circles::Vector{Float64}, ctx::MacContext)
+    length(circles) % 3 == 0 || throw(InexactError(:Int, Int, length(circles) / 3))
+    N = div(length(circles), 3)
+    owned = zeros(Float64, N)
+    exclusive = zeros(Float64, N)
+    area = Ref{Float64}(0.0)
+    check(ccall((:mac_area_by_disk_f64, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+                ctx, circles, length(circles), owned, exclusive, area))
+    return owned, exclusive, area[]
 end
 
 """K candidates as the columns of a 3N x K matrix."""

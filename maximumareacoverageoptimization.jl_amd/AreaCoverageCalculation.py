@@ -16,8 +16,8 @@ import numpy as np
 from ._lib import Context, InexactError, default_context
 from .Base_Functions import Circle
 
-__all__ = ["createPOI", "make_circles", "make_MADS", "calculateArea", "rmvCoveredPOI",
-           "DevicePointList"]
+__all__ = ["createPOI", "make_circles", "make_MADS", "calculateArea", "calculateAreaByDisk",
+           "rmvCoveredPOI", "DevicePointList"]
 
 
 def createPOI(dx: float, dy: float, x_length: float, y_length: float) -> np.ndarray:
@@ -90,6 +90,17 @@ def calculateArea(circles, points) -> float:
     ctx.set_points_records(np.asarray(points, dtype=np.float64).reshape(-1, 5)
                            if np.asarray(points).ndim == 1 else points)
     return ctx.area(c)
+
+
+def calculateAreaByDisk(circles, ctx: Context | None = None):
+    """The credits calculateArea's loop sums (src/AreaCoverageCalculation.jl:67-78: each covered
+    entry goes to the first disk, in index order, that covers it), kept per UAV, on ``ctx``'s
+    point list: ``(owned, exclusive, area)`` with ``owned[i]`` the weight credited to disk i
+    (``sum(owned) == calculateArea``) and ``exclusive[i]`` the weight disk i alone covers, i.e.
+    what the area loses if UAV i is withdrawn."""
+    c = np.asarray(circles, dtype=np.float64)
+    _n_circles(c)
+    return (ctx or default_context()).area_by_disk(c)
 
 
 def rmvCoveredPOI(circles, points):

@@ -62,13 +62,18 @@ def cons3_ok(prev: np.ndarray, x: np.ndarray, d_lim: np.ndarray) -> bool:
 class Simulation:
     """The MPC loop as a stepper (one ``step()`` per timestep t = 1, 2, ...). Point source:
     ``fire`` (GPU CA: its initial points first, one CA step per MPC step), ``firepoints`` (table
-    rows: rows 1..10 initially, then row t+10), or ``initial_points`` alone (static)."""
+    rows: rows 1..10 initially, then row t+10), or ``initial_points`` alone (static).
+    ``attribution=True`` adds ``owned`` and ``exclusive`` (N doubles each, Context.area_by_disk of
+    the step's MADS output on the step's list) to every record."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
-                 shard=None, gather=None, speculate: bool | None = None, device=None):
+                 shard=None, gather=None, speculate: bool | None = None, device=None,
+                 attribution: bool = False):
         self.ctx = ctx
+        # per-UAV attribution of each step's MADS output (one mac_area_by_disk_f64 call per step)
+        self.attribution = bool(attribution)
         self.x_prev = np.asarray(starting_circles, dtype=np.float64).copy()
         self.N = N = self.x_prev.size // 3
         self.tan = math.tan(FOV / 2)
@@ -168,6 +173,8 @@ class Simulation:
                    mads_host_s={k: float(st.get(k, 0.0)) for k in
                                 ("host_enqueue_s", "host_perm_s", "wait_s", "host_post_s")},
                    input=single_input)
+        if self.attribution:   # on the step's (post-removal) list
+            rec["owned"], rec["exclusive"], _ = ctx.area_by_disk(x_out)
         self.records.append(rec)
         self.x_prev = x_out                                              # perfect tracking
         return rec

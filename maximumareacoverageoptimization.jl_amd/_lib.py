@@ -71,6 +71,7 @@ EXPORTS = (
     "mac_mads_poll_ahead", "mac_mads_advance",
     "mac_mads_best_buffer", "mac_best_reduce_dev", "mac_poll_basis_f64",
     "mac_comm_unique_id", "mac_comm_init", "mac_poll_exchange", "mac_exchange_records",
+    "mac_area_by_disk_f64", "mac_area_by_disk_batch_f64", "mac_area_by_disk_dev_f64",
 )
 
 
@@ -146,6 +147,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_poll_best_f64": ([_vp, _dp, _i64, _i64, _dp, ctypes.c_double, _dp, _dp,
                                ctypes.c_double, _dp, _dp, _i64p], _i32),
         "mac_area_batch_dev_f64": ([_vp, _vp, _i64, _i64, _vp, _vp], _i32),
+        "mac_area_by_disk_f64": ([_vp, _dp, _i64, _dp, _dp, _dp], _i32),
+        "mac_area_by_disk_batch_f64": ([_vp, _dp, _i64, _i64, _dp, _dp, _dp], _i32),
+        "mac_area_by_disk_dev_f64": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
         "mac_poll_best_dev_f64": ([_vp, _vp, _i64, _i64, _vp, ctypes.c_double, _vp, _vp,
                                    ctypes.c_double, _i64, _vp, _vp, _vp], _i32),
         "mac_best_fetch": ([_vp, _vp, _vp, _dp, _i64p], _i32),
@@ -499,6 +503,42 @@ class Context:
         out = np.empty(K)
         _check(self._L.mac_area_batch_f64(self._h, _ptr(c), three_n, K, _ptr(out)))
         return out
+
+    def area_by_disk(self, circles):
+        """mac_area_by_disk_f64: (owned[N], exclusive[N], area) of one candidate. owned[i] is the
+        weight of the entries whose first covering disk in index order is i (they sum to the area),
+        exclusive[i] the weight disk i alone covers (area(all) - area(all but i))."""
+        c = _f64(circles).ravel()
+        N = c.size // 3
+        owned = np.zeros(N)
+        excl = np.zeros(N)
+        out = ctypes.c_double()
+        _check(self._L.mac_area_by_disk_f64(self._h, _ptr(c), c.size, _ptr(owned), _ptr(excl),
+                                            ctypes.byref(out)))
+        return owned, excl, out.value
+
+    def area_by_disk_batch(self, cands):
+        """mac_area_by_disk_batch_f64. cands: K x 3N (row k = candidate k). Returns
+        (owned[K, N], exclusive[K, N], area[K])."""
+        c = _f64(cands)
+        if c.ndim != 2:
+            raise ValueError("cands must be K x 3N")
+        K, three_n = c.shape
+        N = three_n // 3
+        owned = np.zeros((K, N))
+        excl = np.zeros((K, N))
+        area = np.zeros(K)
+        _check(self._L.mac_area_by_disk_batch_f64(self._h, _ptr(c), three_n, K, _ptr(owned),
+                                                  _ptr(excl), _ptr(area)))
+        return owned, excl, area
+
+    def area_by_disk_dev(self, d_cands, three_n: int, K: int, d_owned, d_exclusive, d_area,
+                         stream=None) -> None:
+        """mac_area_by_disk_dev_f64: device pointers (torch float64 tensors / ints; any of the three
+        outputs may be None, not all), ordered on `stream`; returns after enqueueing."""
+        _check(self._L.mac_area_by_disk_dev_f64(self._h, _devptr(d_cands), int(three_n), int(K),
+                                                _devptr(d_owned), _devptr(d_exclusive),
+                                                _devptr(d_area), _stream(stream, self.device)))
 
     def objective_batch(self, cands, r_max, penalty: float = 1e5) -> np.ndarray:
         c = _f64(cands)

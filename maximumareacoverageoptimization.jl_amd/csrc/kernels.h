@@ -26,6 +26,8 @@
 //   finalize_kernel       fixed-order sum of per-disk credits (per position, gathered through the
 //                         map) -> area, objective, and the argmin by the last-arriving block
 //   closure_kernel        one candidate in one launch (the per-trial-point objective callback)
+//   by_disk_kernel        the same launch shape keeping the per-disk values: the weight each disk
+//                         owns (first covering disk in index order) and the weight it alone covers
 // (Cross-workgroup hand-offs use agent-scope stores drained before one counter add, never a
 // device-scope fence: that fence writes back the XCD's L2 on gfx950.)
 // An entry is credited to the LOWEST-index disk covering it (exactly-once union count), so the
@@ -41,4 +43,5 @@
 #include "k_final.h"
 #include "k_setup.h"
 #include "k_closure.h"
+#include "k_bydisk.h"
 #include "k_fiw.h"

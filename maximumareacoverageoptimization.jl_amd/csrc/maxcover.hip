@@ -171,6 +171,7 @@ struct Lane {
     uint64_t cl_seq = 0;
     DevBuf cpart, carrive, ctot;               // closure_kernel: credits, arrivals, packed count
     DevBuf clv;                                // closure candidates written by the host (BAR)
+    DevBuf bdpart, bdarrive, bdout;            // by_disk_kernel: owned words, arrivals; host calls' results
     DevBuf prec, cost;                         // prep launch: per-disk records; walk costs
     int um_hist[8] = {};                       // most distinct positions of a disk, last 8 polls
     int walk_hist[8] = {};                     // the walk AUTO would have chosen, last 8 polls
@@ -1750,7 +1751,7 @@ void mac_ctx_destroy(mac_ctx* ctx)
                           &l->lanexp, &l->rows, &l->nboxT, &l->cnt, &l->dlimraw, &l->finblk, &l->finarrive, &l->c32, &l->p32,
                           &l->cpart, &l->carrive, &l->ctot, &l->clv, &l->prec, &l->cost, &l->nboxU,
                           &l->ncountU, &l->orjobs, &l->pd, &l->dead8, &l->frows, &l->fwhint, &l->fwlist, &l->fwcount,
-                          &l->fwsxy, &l->fwsw})
+                          &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout})
             b->release();
         if (l->done) (void)hipEventDestroy(l->done);
 
@@ -3325,6 +3326,149 @@ int32_t mac_area_batch_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t thre
     const int N = (int)(three_n / 3);
     enqueue_eval(ctx, lg.lane, s, matrix_src(d_cands, N), N, (int)K, use_tiled(ctx, N, nullptr, three_n), nullptr,
                  0.0, nullptr, nullptr, nullptr, 1.0, d_area, nullptr, nullptr, 0);
+    return MAC_OK;
+    ABI_END
+}
+
+// ---- per-disk attribution (k_bydisk.h): owned / exclusive weight per disk and the area, one launch
+// per 65535 candidates (grid.y)
+
+static int32_t by_disk_check(mac_ctx* ctx, const void* cands, int64_t three_n, int64_t K, const void* owned,
+                             const void* excl, const void* area)
+{
+    int32_t rc = check_common(ctx, three_n, K);
+    if (rc) return rc;
+    if (three_n / 3 > kClosureMaxN)
+        return fail(MAC_E_INVAL, "mac_area_by_disk: N = " + std::to_string(three_n / 3) + " > " +
+                                     std::to_string(kClosureMaxN) + " UAVs (the per-disk kernel's limit)");
+    if (K == 0) return MAC_OK;
+    if (!cands && three_n > 0) return fail(MAC_E_INVAL, "null candidates");
+    if (!owned && !excl && !area) return fail(MAC_E_INVAL, "no output given (owned, exclusive and area all null)");
+    return MAC_OK;
+}
+
+static void by_disk_enqueue(mac_ctx* ctx, Lane* L, hipStream_t s, const double* d_cands, int N, int64_t K,
+                            double* d_owned, double* d_excl, double* d_area)
+{
+    constexpr int64_t kMaxY = 65535;   // grid.y
+    const int64_t Kc = std::min(K, kMaxY);
+    L->bdpart.reserve(sizeof(unsigned long long) * (size_t)N * (size_t)Kc);
+    // zero once; the last workgroup of each candidate resets its counter
+    if (L->bdarrive.grow(sizeof(unsigned) * (size_t)Kc)) HCK(hipMemsetAsync(L->bdarrive.p, 0, L->bdarrive.cap, s));
+    const int nwg = (N + kClosureDisksPerWG - 1) / kClosureDisksPerWG;   // a wave per disk
+    for (int64_t k0 = 0; k0 < K; k0 += kMaxY) {
+        const int64_t B = std::min(kMaxY, K - k0);
+        int64_t ts_a = -1;
+        uint64_t* ts = nullptr;
+        if (ctx->profile) {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            if (ctx->stamp_used + (int64_t)nwg * B <= ctx->stamp_cap) {
+                ts_a = ctx->stamp_used;
+                ctx->stamp_used += (int64_t)nwg * B;
+                ts = ctx->stamps.as<uint64_t>() + 2 * ts_a;
+            }
+        }
+        const size_t o = (size_t)k0 * (size_t)N;
+        const ByDiskOut bo{d_owned ? d_owned + o : nullptr, d_excl ? d_excl + o : nullptr,
+                           d_area ? d_area + k0 : nullptr, L->bdpart.as<unsigned long long>(),
+                           L->bdarrive.as<unsigned>()};
+        hipLaunchKernelGGL(by_disk_kernel, dim3((unsigned)nwg, (unsigned)B), dim3(kBlock),
+                           (uint32_t)closure_lds_bytes(N), s, ts, d_cands + 3 * o, N, ctx->grid,
+                           ctx->xys.as<double2>(), ctx->ws.as<double>(), ctx->off.as<int32_t>(),
+                           ctx->w_uniform ? 1 : 0, ctx->w0, bo);
+        HCK(hipGetLastError());
+        if (ts) {
+            std::lock_guard<std::mutex> lk(ctx->mu);
+            ctx->prof.push_back({ts_a, (int64_t)nwg * B, -1, 0, B, nullptr, MAC_ALGO_TILED});
+        }
+    }
+}
+
+// Host-pointer calls: upload, one launch, one download, the lane's stream synchronised.
+static int32_t by_disk_host(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K, double* owned_out,
+                            double* excl_out, double* area_out)
+{
+    int32_t rc = by_disk_check(ctx, cands, three_n, K, owned_out, excl_out, area_out);
+    if (rc || K == 0) return rc;
+    const int N = (int)(three_n / 3);
+    const size_t nk = (size_t)N * (size_t)K;
+    if (three_n == 0 || ctx->M == 0) {   // nothing to cover, or nothing covering
+        if (owned_out) std::fill(owned_out, owned_out + nk, 0.0);
+        if (excl_out) std::fill(excl_out, excl_out + nk, 0.0);
+        if (area_out) std::fill(area_out, area_out + K, 0.0);
+        return MAC_OK;
+    }
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t in_bytes = sizeof(double) * (size_t)three_n * (size_t)K;
+    const size_t nO = owned_out ? nk : 0, nX = excl_out ? nk : 0, nA = area_out ? (size_t)K : 0;
+    const size_t out_bytes = sizeof(double) * (nO + nX + nA);
+    L->cands.reserve(in_bytes);
+    L->bdout.reserve(out_bytes);   // [owned][exclusive][area], one download
+    double* d_o = L->bdout.as<double>();
+    double* d_x = d_o + nO;
+    double* d_a = d_x + nX;
+    const bool staged = std::max(in_bytes, out_bytes) <= ((size_t)64 << 20);
+    if (staged) {
+        L->h_io.reserve(std::max<size_t>(std::max(in_bytes, out_bytes), 64));
+        staged_upload(cands, L->h_io.p, L->cands.p, in_bytes, s);
+    } else {
+        HCK(hipMemcpyAsync(L->cands.p, cands, in_bytes, hipMemcpyHostToDevice, s));
+    }
+    by_disk_enqueue(ctx, L, s, L->cands.as<double>(), N, K, nO ? d_o : nullptr, nX ? d_x : nullptr,
+                    nA ? d_a : nullptr);
+    if (staged) {   // (the upload has completed before the kernel ran: the staging is free again)
+        HCK(hipMemcpyAsync(L->h_io.p, d_o, out_bytes, hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+        const double* h = (const double*)L->h_io.p;
+        if (nO) std::memcpy(owned_out, h, sizeof(double) * nO);
+        if (nX) std::memcpy(excl_out, h + nO, sizeof(double) * nX);
+        if (nA) std::memcpy(area_out, h + nO + nX, sizeof(double) * nA);
+    } else {
+        if (nO) HCK(hipMemcpyAsync(owned_out, d_o, sizeof(double) * nO, hipMemcpyDeviceToHost, s));
+        if (nX) HCK(hipMemcpyAsync(excl_out, d_x, sizeof(double) * nX, hipMemcpyDeviceToHost, s));
+        if (nA) HCK(hipMemcpyAsync(area_out, d_a, sizeof(double) * nA, hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+    }
+    return MAC_OK;
+}
+
+int32_t mac_area_by_disk_f64(mac_ctx* ctx, const double* circles, int64_t three_n, double* owned_out,
+                             double* exclusive_out, double* area_out)
+{
+    ABI_BEGIN
+    return by_disk_host(ctx, circles, three_n, 1, owned_out, exclusive_out, area_out);
+    ABI_END
+}
+
+int32_t mac_area_by_disk_batch_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                                   double* owned_out, double* exclusive_out, double* area_out)
+{
+    ABI_BEGIN
+    return by_disk_host(ctx, cands, three_n, K, owned_out, exclusive_out, area_out);
+    ABI_END
+}
+
+int32_t mac_area_by_disk_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
+                                 double* d_owned, double* d_exclusive, double* d_area, void* stream)
+{
+    ABI_BEGIN
+    int32_t rc = by_disk_check(ctx, d_cands, three_n, K, d_owned, d_exclusive, d_area);
+    if (rc || K == 0) return rc;
+    set_device(ctx);
+    hipStream_t s = (hipStream_t)stream;   // NULL: HIP's null stream
+    const int N = (int)(three_n / 3);
+    const size_t nk = sizeof(double) * (size_t)N * (size_t)K;
+    if (three_n == 0 || ctx->M == 0) {
+        if (d_owned && nk) HCK(hipMemsetAsync(d_owned, 0, nk, s));
+        if (d_exclusive && nk) HCK(hipMemsetAsync(d_exclusive, 0, nk, s));
+        if (d_area) HCK(hipMemsetAsync(d_area, 0, sizeof(double) * (size_t)K, s));
+        return MAC_OK;
+    }
+    LaneGuard lg(ctx, s);
+    by_disk_enqueue(ctx, lg.lane, s, d_cands, N, K, d_owned, d_exclusive, d_area);
     return MAC_OK;
     ABI_END
 }
