@@ -33,6 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "predicate.h"
 #include "k_common.h"
 #include "k_prep.h"
@@ -69,8 +71,9 @@ constexpr int kFwHints = 4;
 
 // The shared entries a disk hands to fin2_kernel: a disk with at most kFwHand lower neighbours and
 // kFwShCap shared entries appends one 16-B record {disk, neighbours | entries << 8, neighbour ids
-// 0 | 1 << 16, 2 | 3 << 16} to a compact list (any order: fin2 sorts it by disk; the count is
-// zeroed by the next poll's prep launch), else decides them in place
+// 0 | 1 << 16, 2 | 3 << 16} to a compact list (any order: fin2 sorts weighted lists by disk and takes
+// equal-weight ones as they come; the count is zeroed by the next poll's prep launch), else decides
+// them in place
 constexpr int kFwHand = 4;
 constexpr int kF2ListCap = 1024;   // listed disks fin2_kernel takes (the rest decide in place)
 struct FwShared {
@@ -161,15 +164,21 @@ __device__ __forceinline__ DiskRec key_disk(const CandSrc& s, uint32_t key, int 
 #ifdef MAC_DIAG
 __device__ uint64_t g_diag_fiw[16 * 65536];  // diagnostic build only: per-disk phase stamps
 #define MAC_FW_STAMP(q) if (threadIdx.x == 0 && i < 65536) g_diag_fiw[16 * i + (q)] = __builtin_amdgcn_s_memrealtime()
-__device__ uint64_t g_diag_f2[8 * 4096];      // per fin2 block
+__device__ uint64_t g_diag_f2[8 * 4096];      // per fin2 block: stamps 0..5, [6] listed disks | entries << 32, [7] last
 #define MAC_F2_STAMP(q)                                                                      \
     if (threadIdx.x == 0 && blockIdx.x < 4096) {                                             \
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                          \
         g_diag_f2[8 * blockIdx.x + (q)] = __builtin_amdgcn_s_memrealtime();                  \
     }
+// While fin2's rows are in flight a stamp is only taken (no vmcnt wait, no store: a pending store
+// would turn the list's counted wait into a full one) and put down once they have been added up
+#define MAC_F2_NOW() __builtin_amdgcn_s_memrealtime()
+#define MAC_F2_PUT(q, v) if (threadIdx.x == 0 && blockIdx.x < 4096) g_diag_f2[8 * blockIdx.x + (q)] = (v)
 #else
 #define MAC_FW_STAMP(q)
 #define MAC_F2_STAMP(q)
+#define MAC_F2_NOW() 0
+#define MAC_F2_PUT(q, v)
 #endif
 
 // per-position / per-candidate credit: exact integer counts (every entry weighs the same) or fp64
@@ -1081,10 +1090,20 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
 // Block = C candidates x (1024 / C) row groups: thread (c, g) sums rows g, g + G, ... of candidate
 // kb + c, all of its rows in flight at once (u32 counts: exact in any order; f64 credits: this
 // fixed order), then the G group sums in group order. Then the shared entries the disks handed off
-// (FwShared's list, sorted by disk), in batches of whole disks (at most kF2Slots disk records): per
-// slot and candidate the disk from its key word (exact doubles), per (entry, candidate) the
-// decision — disk i covers it, none of its listed lower neighbours does — with each disk's entries
-// split over the row groups (its records held in registers) and added in that group's fixed order.
+// (FwShared's list), in batches of whole disks (at most kF2Slots disk records): per slot and
+// candidate the disk from its key word (exact doubles), per (entry, candidate) the decision — disk i
+// covers it, none of its listed lower neighbours does.
+//   * Latency: the list's count and first records, the penalty, the failure byte and the first row
+//     batch are issued together and nothing is looked at before the rows are out. The list phase
+//     (LDS only, lds_barrier()) runs while the rows are in flight; then the second round trip (key
+//     words, candidate 0's disks, the entries) is issued, and only then are the rows added up.
+//   * Counts (every entry weighs the same): the listed disks are taken in arrival order (integer
+//     sums: any order), each staged entry carries its disk's slot and neighbour count (etag), and
+//     thread (c, g) walks the chunk's entries g, g + G, ... in one loop over all listed disks.
+//   * Weighted lists: the list is sorted by disk and each disk's entries are split over the row
+//     groups and added in that group's fixed order, disk after disk (part of the fp64 result).
+//   * Slot -> disk (sdisk) and entry -> slot are filled from per-disk ranges (one writer a disk for
+//     the slots, the waves split over the disks for the entries): no search.
 // obj_k = -area_k + vp_k; the argmin by the last-arriving block (k_final.h finalize_argmin), which
 // also copies the fused kernel's hint words to the lane's mapped host memory (maxcover.hip
 // enqueue_eval reads them before the next poll).
@@ -1127,55 +1146,90 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     // one round trip: the list's count and first kF2Pre records, the candidate's penalty and
     // failure byte, and its rows (kF2R per thread in flight at once; more in later batches)
     constexpr int kF2R = 16;
-    const int lc = min(*sd.count, min(kF2List, N));
-    const int4 lr0 = t < kF2Pre ? sd.list[min(t, N - 1)] : make_int4(0, 0, 0, 0);
+    // (the count and the failure byte are loaded without a branch and first looked at below, after
+    // the rows' issue: a use here would wait for them before the rows are sent)
+    int lcraw = *sd.count;
+    // (weighted lists read their records after the rows' issue instead: held in registers across
+    // it, this record was spilled to scratch and waited for before the rows went out)
+    const int4 lr0 = kCounts && t < kF2Pre ? sd.list[min(t, N - 1)] : make_int4(0, 0, 0, 0);
     const double vpk = (vp && gq == 0 && k < K) ? vp[k] : 0.0;
-    const bool cdead = !(k < K) || !run || (sd.dead && sd.dead[kc]);
+    int dbyte = *(sd.dead ? sd.dead + kc : reinterpret_cast<const uint8_t*>(sd.count));
     uint64_t s = 0;
     double sf = 0.0;
-    if (k < K) {
-        for (int r = gq; r < N; r += kF2R * G) {
-            if constexpr (kCounts) {
-                unsigned v[kF2R];
+    // the first row batch is issued here and added up only in sum_rows(): with a hand-off list the
+    // loads stay in flight through the list phase (LDS only) and the second round trip's issue
+    // (clamped addresses, no branch: rows past N and candidates past K read a valid word, unused)
+    typename FwAcc<kCounts>::T v0[kF2R];
 #pragma unroll
-                for (int b = 0; b < kF2R; ++b) {
-                    const int rr = r + b * G;
-                    v[b] = rr < N ? crow[(int64_t)rr * ldk + k] : 0u;
+    for (int b = 0; b < kF2R; ++b) {
+        const int64_t at = (int64_t)min(gq + b * G, N - 1) * ldk + kc;
+        if constexpr (kCounts) v0[b] = crow[at];
+        else v0[b] = frow[at];
+    }
+    // The empty asm keeps both uses below the rows' issue; the language does not promise that order,
+    // so after a compiler change check the ISA (make asm, or hipcc -S --offload-device-only): in
+    // fin2_kernel<true> the count, the record, the penalty, the byte and 16 row loads stand back to
+    // back, the first wait after them is s_waitcnt vmcnt(16), and on the matrix-source path no
+    // vmcnt(0) stands before the key-word, base and entry loads of the second round trip.
+    asm volatile("" : "+v"(lcraw), "+v"(dbyte) : : "memory");   // (the rows are issued above this line)
+    const int lc = min(__builtin_amdgcn_readfirstlane(lcraw), min(kF2List, N));
+    const bool cdead = !(k < K) || !run || (sd.dead && dbyte != 0);
+    auto sum_rows = [&]() {
+        if constexpr (kCounts) {
+#pragma unroll
+            for (int b = 0; b < kF2R; ++b) s += gq + b * G < N ? v0[b] : 0u;
+        } else {
+            double bs = 0.0;
+#pragma unroll
+            for (int b = 0; b < kF2R; ++b) bs += gq + b * G < N ? v0[b] : 0.0;
+            sf += bs;
+        }
+        if (k < K) {   // (N > kF2R * G: the later batches, one round trip each)
+            for (int r = gq + kF2R * G; r < N; r += kF2R * G) {
+                if constexpr (kCounts) {
+                    unsigned v[kF2R];
+#pragma unroll
+                    for (int b = 0; b < kF2R; ++b) {
+                        const int rr = r + b * G;
+                        v[b] = rr < N ? crow[(int64_t)rr * ldk + k] : 0u;
+                    }
+#pragma unroll
+                    for (int b = 0; b < kF2R; ++b) s += v[b];
+                } else {
+                    double v[kF2R];
+#pragma unroll
+                    for (int b = 0; b < kF2R; ++b) {
+                        const int rr = r + b * G;
+                        v[b] = rr < N ? frow[(int64_t)rr * ldk + k] : 0.0;
+                    }
+                    double bs = 0.0;
+#pragma unroll
+                    for (int b = 0; b < kF2R; ++b) bs += v[b];
+                    sf += bs;
                 }
-#pragma unroll
-                for (int b = 0; b < kF2R; ++b) s += v[b];
-            } else {
-                double v[kF2R];
-#pragma unroll
-                for (int b = 0; b < kF2R; ++b) {
-                    const int rr = r + b * G;
-                    v[b] = rr < N ? frow[(int64_t)rr * ldk + k] : 0.0;
-                }
-                double bs = 0.0;
-#pragma unroll
-                for (int b = 0; b < kF2R; ++b) bs += v[b];
-                sf += bs;
             }
         }
+    };
+    if (!(lc > 0 && run)) {   // (uniform) no hand-off list: one round trip, then the reduction
+        sum_rows();
+        MAC_F2_STAMP(1);
+        MAC_F2_STAMP(2);
+        MAC_F2_PUT(6, (uint64_t)0);
     }
-    MAC_F2_STAMP(1);
     // ---- the handed-off shared entries (lc: uniform)
     if (lc > 0 && run) {
-        __shared__ int4 lraw[kF2List];
+        __shared__ int4 lraw[kF2List];                           // (weighted lists only: the sort)
         __shared__ int flist[kF2List], fnc[kF2List], fsh[kF2List];
         __shared__ int fids[kF2List][kFwHand];
         __shared__ int bslot[kF2List + 1], bent[kF2List + 1];   // per listed disk: first slot, entry
+        __shared__ int sdisk[kF2Slots];                          // per slot of the batch: its disk
         __shared__ double srec[kF2Slots][3][C];                  // per slot and candidate: x, y, T
         __shared__ double2 sxy[kF2Ent];
-        __shared__ double swt[kF2Ent];
-        __shared__ int nbat;
-        for (int q = t; q < lc; q += kF2Threads) lraw[q] = q < kF2Pre ? lr0 : sd.list[q];
-        __syncthreads();
-        // sorted by disk: each record's rank among the listed disks (distinct ids)
-        for (int q = t; q < lc; q += kF2Threads) {
-            const int4 r = lraw[q];
-            int rk = 0;
-            for (int o = 0; o < lc; ++o) rk += lraw[o].x < r.x;
+        __shared__ double swt[kF2Ent];                           // (weighted lists only)
+        __shared__ uint16_t etag[kF2Ent];   // (counts only) per entry: its disk's slot | neighbours << 8
+        const int lane = t & (kWave - 1);
+        // Every barrier from here to the row sums is lds_barrier(): the rows stay in flight.
+        auto put = [&](int rk, const int4 r) {
             flist[rk] = r.x;
             fnc[rk] = r.y & 0xFF;
             fsh[rk] = r.y >> 8;
@@ -1183,146 +1237,240 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
             fids[rk][1] = (int)((unsigned)r.z >> 16);
             fids[rk][2] = r.w & 0xFFFF;
             fids[rk][3] = (int)((unsigned)r.w >> 16);
-        }
-        __syncthreads();
-        if (t == 0) {   // slots and entries per listed disk
-            int sl = 0, en = 0;
-            for (int q = 0; q < lc; ++q) {
-                bslot[q] = sl;
-                bent[q] = en;
-                sl += 1 + fnc[q];
-                en += fsh[q];
+        };
+        if constexpr (kCounts) {
+            // integer credits: any order of the listed disks gives the same sums (arrival order)
+            for (int q = t; q < lc; q += kF2Threads) put(q, q < kF2Pre ? lr0 : sd.list[q]);
+        } else {
+            for (int q = t; q < lc; q += kF2Threads) lraw[q] = sd.list[q];
+            lds_barrier();
+            // sorted by disk: each record's rank among the listed disks (distinct ids)
+            for (int q = t; q < lc; q += kF2Threads) {
+                const int4 r = lraw[q];
+                int rk = 0;
+                for (int o = 0; o < lc; ++o) rk += lraw[o].x < r.x;
+                put(rk, r);
             }
-            bslot[lc] = sl;
-            bent[lc] = en;
         }
-        __syncthreads();
-        MAC_F2_STAMP(2);
-        for (int q0 = 0; q0 < lc;) {
-            // the batch: listed disks [q0, q1) whose records fit kF2Slots (one disk always fits)
+        lds_barrier();
+        // slots and entries per listed disk (a wave scan, 64 disks a step), and the first batch's
+        // slot owners: a disk whose slots end within kF2Slots is in it
+        if (t < kWave) {
+            int cs = 0, ce = 0;
+            for (int base = 0; base < lc; base += kWave) {
+                const int q = base + t;
+                const bool in = q < lc;
+                const int qn = in ? min(fnc[q], kFwHand) : 0;
+                const int qs = in ? 1 + qn : 0, qe = in ? fsh[q] : 0;
+                int is = qs, ie = qe;
+#pragma unroll
+                for (int o = 1; o < kWave; o <<= 1) {
+                    const int us = __shfl_up(is, o, kWave), ue = __shfl_up(ie, o, kWave);
+                    if (t >= o) {
+                        is += us;
+                        ie += ue;
+                    }
+                }
+                if (in) {
+                    const int b = cs + is - qs;
+                    bslot[q] = b;
+                    bent[q] = ce + ie - qe;
+                    if (cs + is <= kF2Slots) {
+                        sdisk[b] = flist[q];
+#pragma unroll
+                        for (int m = 0; m < kFwHand; ++m)
+                            if (m < qn) sdisk[b + 1 + m] = fids[q][m];
+                    }
+                }
+                cs += __shfl(is, kWave - 1, kWave);
+                ce += __shfl(ie, kWave - 1, kWave);
+            }
             if (t == 0) {
-                int q1 = q0 + 1;
-                while (q1 < lc && bslot[q1 + 1] - bslot[q0] <= kF2Slots) ++q1;
-                nbat = q1;
+                bslot[lc] = cs;
+                bent[lc] = ce;
             }
-            __syncthreads();
-            const int q1 = nbat;
+        }
+        lds_barrier();
+        [[maybe_unused]] const uint64_t t_list = MAC_F2_NOW();   // (no store: the rows are in flight)
+        // the batch from q0: listed disks [q0, q1) whose records fit kF2Slots (one disk always
+        // fits; at most kWave disks, a slot or more each): every wave counts them for itself
+        auto batch_end = [&](int q0) {
+            const int q = min(q0 + 1 + lane, lc);
+            const bool ok = q0 + 1 + lane <= lc && bslot[q] - bslot[q0] <= kF2Slots;
+            return q0 + max(1, (int)__popcll(__ballot(ok)));
+        };
+        // a chunk's entries [e0, e0 + ne) of the batch into LDS, by per-disk ranges: the waves
+        // split the listed disks (several waves a disk when there are few), lanes its entries
+        auto stage = [&](int q0, int q1, int sl0, int e0, int ne) {
+            constexpr int kW = kF2Threads / kWave, kU = 4;
+            const int w = __builtin_amdgcn_readfirstlane(t / kWave);
+            const int nd = q1 - q0, parts = max(1, kW / nd);
+            for (int wi = w; wi < nd * parts; wi += kW) {
+                const int lq = q0 + wi / parts, p = wi % parts;
+                const int d0 = bent[lq];
+                const int ja = max(d0, e0) - d0, jb = min(bent[lq + 1], e0 + ne) - d0;
+                if (ja >= jb) continue;
+                const int64_t sb = (int64_t)flist[lq] * kFwShCap;
+                const int o = d0 - e0;   // (the chunk position of the disk's entry 0)
+                [[maybe_unused]] const uint16_t tag = (uint16_t)((bslot[lq] - sl0) | (min(fnc[lq], kFwHand) << 8));
+                const int st = parts * kWave;
+                for (int j = ja + p * kWave + lane; j < jb; j += kU * st) {
+                    double2 vxy[kU];
+                    [[maybe_unused]] double vw[kU];
+#pragma unroll
+                    for (int u = 0; u < kU; ++u) {   // (clamped: every load issued, no branch)
+                        const int jc = min(j + u * st, jb - 1);
+                        vxy[u] = sd.xy[sb + jc];
+                        if constexpr (!kCounts) vw[u] = sd.w[sb + jc];
+                    }
+#pragma unroll
+                    // Past the range a lane writes the range's last entry again: a deliberate
+                    // same-value LDS race (several lanes and waves may store to that one slot at
+                    // once), safe because every writer loaded the same global words for it; it
+                    // keeps the loads above free of branches (one round trip, not one a load).
+                    for (int u = 0; u < kU; ++u) {
+                        const int jc = min(j + u * st, jb - 1);
+                        sxy[o + jc] = vxy[u];
+                        if constexpr (kCounts) etag[o + jc] = tag;
+                        else swt[o + jc] = vw[u];
+                    }
+                }
+            }
+        };
+        // one batch; first: the launch's first batch, which also adds up the rows
+        auto batch = [&](auto first, const int q0) {
+            const int q1 = batch_end(q0);
             const int sl0 = bslot[q0], ns = bslot[q1] - sl0;
             const int e0all = bent[q0], e1all = bent[q1];
-            // the first chunk's entries, loaded before the records' keys (one round trip for both)
-            constexpr int kEPT = kF2Ent / kF2Threads;
-            double2 exy[kEPT];
-            double ew[kEPT];
-            {
-                const int ne = min(kF2Ent, e1all - e0all);
-#pragma unroll
-                for (int r = 0; r < kEPT; ++r) {
-                    const int e = t + r * kF2Threads;
-                    exy[r] = make_double2(0.0, 0.0);
-                    ew[r] = 0.0;
-                    if (e < ne) {
-                        const int eg = e0all + e;   // the listed disk holding it
-                        int lo = q0, hi = q1 - 1;
-                        while (lo < hi) {
-                            const int mid = (lo + hi + 1) >> 1;
-                            if (bent[mid] <= eg) lo = mid; else hi = mid - 1;
-                        }
-                        const int64_t se = (int64_t)flist[lo] * kFwShCap + (eg - bent[lo]);
-                        exy[r] = sd.xy[se];
-                        if constexpr (!kCounts) ew[r] = sd.w[se];
-                    }
-                }
+            // the second round trip: per slot and candidate the key word and candidate 0's disk
+            // (thread t: slot t / C, its own candidate; ns * C <= kF2Threads), then the entries
+            const int sl = t / C;
+            const bool rec = sl < ns;
+            const int jj = sdisk[rec ? sl : 0];
+            const uint32_t key = src.keysP[(int64_t)jj * src.ldk + kc];
+            const double bx = src_val(src, 0, jj, N), by = src_val(src, 0, N + jj, N),
+                         br = src_val(src, 0, 2 * N + jj, N);
+            int e0 = e0all, ne = min(kF2Ent, e1all - e0);
+            stage(q0, q1, sl0, e0, ne);
+            if constexpr (decltype(first)::value) sum_rows();
+            if (rec) {
+                const DiskRec d = key_disk(src, key, jj, kc, N, bx, by, br);
+                srec[sl][0][c] = d.cx;
+                srec[sl][1][c] = d.cy;
+                srec[sl][2][c] = d.T;
             }
-            // per slot and candidate: the disk (its key word, candidate 0's disk)
-            for (int q = t; q < ns * C; q += kF2Threads) {
-                const int sl = q / C, cc = q % C;
-                int lo = q0, hi = q1 - 1;   // the listed disk holding slot sl0 + sl
-                while (lo < hi) {
-                    const int mid = (lo + hi + 1) >> 1;
-                    if (bslot[mid] - sl0 <= sl) lo = mid; else hi = mid - 1;
-                }
-                const int m = sl - (bslot[lo] - sl0);
-                const int jj = m == 0 ? flist[lo] : fids[lo][m - 1];
-                const int kk = min(cb * C + cc, K - 1);
-                const uint32_t key = src.keysP[(int64_t)jj * src.ldk + kk];
-                const DiskRec d = key_disk(src, key, jj, kk, N, src_val(src, 0, jj, N),
-                                           src_val(src, 0, N + jj, N), src_val(src, 0, 2 * N + jj, N));
-                srec[sl][0][cc] = d.cx;
-                srec[sl][1][cc] = d.cy;
-                srec[sl][2][cc] = d.T;
-            }
-            for (int e0 = e0all; e0 < e1all; e0 += kF2Ent) {
-                const int ne = min(kF2Ent, e1all - e0);
-                if (e0 == e0all) {
-#pragma unroll
-                    for (int r = 0; r < kEPT; ++r) {
-                        const int e = t + r * kF2Threads;
-                        if (e < ne) {
-                            sxy[e] = exy[r];
-                            swt[e] = ew[r];
-                        }
-                    }
-                } else {
-                    for (int e = t; e < ne; e += kF2Threads) {
-                        const int eg = e0 + e;
-                        int lo = q0, hi = q1 - 1;
-                        while (lo < hi) {
-                            const int mid = (lo + hi + 1) >> 1;
-                            if (bent[mid] <= eg) lo = mid; else hi = mid - 1;
-                        }
-                        const int64_t se = (int64_t)flist[lo] * kFwShCap + (eg - bent[lo]);
-                        sxy[e] = sd.xy[se];
-                        swt[e] = kCounts ? 0.0 : sd.w[se];
+            for (;;) {
+                lds_barrier();
+                if constexpr (decltype(first)::value) {
+                    if (e0 == e0all) {
+                        MAC_F2_PUT(1, t_list);
+                        MAC_F2_PUT(6, (uint64_t)lc | ((uint64_t)bent[lc] << 32));   // (the listed disks, entries)
+                        MAC_F2_STAMP(2);
                     }
                 }
-                __syncthreads();
-                MAC_F2_STAMP(3);
-                // per listed disk: its records and its neighbours' in registers, then its entries
-                // of this chunk, split over the row groups (group gq: entries gq, gq + G, ...)
                 if (!cdead) {
-                    for (int lq = q0; lq < q1; ++lq) {
-                        const int ea = max(bent[lq], e0) - e0, eb = min(bent[lq + 1], e0 + ne) - e0;
-                        if (ea >= eb) continue;
-                        const int b = bslot[lq] - sl0, ncq = fnc[lq];
-                        const double cx = srec[b][0][c], cy = srec[b][1][c], T = srec[b][2][c];
-                        double nx[kFwHand], ny[kFwHand], nT[kFwHand];
-#pragma unroll
-                        for (int m = 0; m < kFwHand; ++m) {
-                            const bool in = m < ncq;
-                            nx[m] = in ? srec[b + 1 + m][0][c] : 0.0;
-                            ny[m] = in ? srec[b + 1 + m][1][c] : 0.0;
-                            nT[m] = in ? srec[b + 1 + m][2][c] : -1.0;   // (never covers)
-                        }
-                        // four entries per step, their LDS reads issued together
+                    if constexpr (kCounts) {
+                        // one loop over the chunk's entries gq, gq + G, ... of every listed disk,
+                        // four a step: their coordinates and tags read together, then their
+                        // disks' records and first neighbours' together (two LDS round trips a
+                        // step); further neighbours (rare) only for an entry still undecided
                         constexpr int kU = 4;
-                        for (int e = ea + gq; e < eb; e += kU * G) {
+                        for (int e = gq; e < ne; e += kU * G) {
                             double2 pp[kU];
-#pragma unroll
-                            for (int u = 0; u < kU; ++u)
-                                pp[u] = e + u * G < eb ? sxy[e + u * G] : make_double2(0.0, 0.0);
+                            int tg[kU];
 #pragma unroll
                             for (int u = 0; u < kU; ++u) {
-                                if (!(e + u * G < eb)) break;
-                                const double2 p = pp[u];
-                                if (!(sqdist(p.x, p.y, cx, cy) <= T)) continue;
-                                bool stolen = false;
+                                const int ee = min(e + u * G, ne - 1);
+                                pp[u] = sxy[ee];
+                                tg[u] = etag[ee];
+                            }
+                            double ox[kU], oy[kU], oT[kU], px[kU], py[kU], pT[kU];
 #pragma unroll
-                                for (int m = 0; m < kFwHand; ++m)   // (ncq: uniform; usually 1)
-                                    if (m < ncq && !stolen) stolen = sqdist(p.x, p.y, nx[m], ny[m]) <= nT[m];
-                                if (!stolen) {
-                                    if constexpr (kCounts) s += 1;
-                                    else sf += swt[e + u * G];
+                            for (int u = 0; u < kU; ++u) {
+                                const int b = tg[u] & 0xFF, b1 = b + ((tg[u] >> 8) > 0 ? 1 : 0);
+                                ox[u] = srec[b][0][c];
+                                oy[u] = srec[b][1][c];
+                                oT[u] = srec[b][2][c];
+                                px[u] = srec[b1][0][c];
+                                py[u] = srec[b1][1][c];
+                                pT[u] = srec[b1][2][c];
+                            }
+#pragma unroll
+                            for (int u = 0; u < kU; ++u) {
+                                const double2 p = pp[u];
+                                const int b = tg[u] & 0xFF, ncq = tg[u] >> 8;
+                                bool cnt = e + u * G < ne && sqdist(p.x, p.y, ox[u], oy[u]) <= oT[u];
+                                if (ncq > 0 && sqdist(p.x, p.y, px[u], py[u]) <= pT[u]) cnt = false;
+                                if (cnt && ncq > 1) {
+                                    for (int m = 1; m < ncq && cnt; ++m)
+                                        cnt = !(sqdist(p.x, p.y, srec[b + 1 + m][0][c], srec[b + 1 + m][1][c]) <=
+                                                srec[b + 1 + m][2][c]);
+                                }
+                                s += cnt ? 1 : 0;
+                            }
+                        }
+                    } else {
+                        // per listed disk: its records and its neighbours' in registers, then its
+                        // entries of this chunk, split over the row groups (group gq: entries gq,
+                        // gq + G, ...): this order is part of the fp64 sum
+                        for (int lq = q0; lq < q1; ++lq) {
+                            const int ea = max(bent[lq], e0) - e0, eb = min(bent[lq + 1], e0 + ne) - e0;
+                            if (ea >= eb) continue;
+                            const int b = bslot[lq] - sl0, ncq = fnc[lq];
+                            const double cx = srec[b][0][c], cy = srec[b][1][c], T = srec[b][2][c];
+                            double nx[kFwHand], ny[kFwHand], nT[kFwHand];
+#pragma unroll
+                            for (int m = 0; m < kFwHand; ++m) {
+                                const bool in = m < ncq;
+                                nx[m] = in ? srec[b + 1 + m][0][c] : 0.0;
+                                ny[m] = in ? srec[b + 1 + m][1][c] : 0.0;
+                                nT[m] = in ? srec[b + 1 + m][2][c] : -1.0;   // (never covers)
+                            }
+                            // four entries per step, their LDS reads issued together
+                            constexpr int kU = 4;
+                            for (int e = ea + gq; e < eb; e += kU * G) {
+                                double2 pp[kU];
+#pragma unroll
+                                for (int u = 0; u < kU; ++u)
+                                    pp[u] = e + u * G < eb ? sxy[e + u * G] : make_double2(0.0, 0.0);
+#pragma unroll
+                                for (int u = 0; u < kU; ++u) {
+                                    if (!(e + u * G < eb)) break;
+                                    const double2 p = pp[u];
+                                    if (!(sqdist(p.x, p.y, cx, cy) <= T)) continue;
+                                    bool stolen = false;
+#pragma unroll
+                                    for (int m = 0; m < kFwHand; ++m)   // (ncq: uniform; usually 1)
+                                        if (m < ncq && !stolen) stolen = sqdist(p.x, p.y, nx[m], ny[m]) <= nT[m];
+                                    if (!stolen) sf += swt[e + u * G];
                                 }
                             }
                         }
                     }
                 }
-                __syncthreads();
+                e0 += kF2Ent;
+                if (e0 >= e1all) break;
+                lds_barrier();   // (the chunk is reused)
+                ne = min(kF2Ent, e1all - e0);
+                stage(q0, q1, sl0, e0, ne);
             }
-            q0 = q1;
+            return q1;
+        };
+        int q0 = batch(std::true_type{}, 0);
+        while (q0 < lc) {
+            // the next batch's slot owners, one writer per listed disk (sdisk was last read
+            // before the decisions' barrier)
+            const int q1 = batch_end(q0), sl0 = bslot[q0];
+            for (int lq = q0 + t; lq < q1; lq += kF2Threads) {
+                const int b = bslot[lq] - sl0, qn = min(fnc[lq], kFwHand);
+                sdisk[b] = flist[lq];
+                for (int m = 0; m < qn; ++m) sdisk[b + 1 + m] = fids[lq][m];
+            }
+            lds_barrier();   // (and the records and the chunk are reused)
+            q0 = batch(std::false_type{}, q0);
         }
     }
-    MAC_F2_STAMP(4);
+    MAC_F2_STAMP(3);
     double o = __builtin_inf();
     if constexpr (kCounts) {
         ired[gq][c] = s;
@@ -1348,14 +1496,14 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
             if (obj_out) obj_out[k] = o;
         }
     }
-    MAC_F2_STAMP(5);
+    MAC_F2_STAMP(4);
     if (fb.best && t < kWave) {
         [[maybe_unused]] const bool last = finalize_argmin<C>(fb, o, k, k < K);   // (+ the hint words)
 #ifdef MAC_DIAG
         if (t == 0 && blockIdx.x < 4096) g_diag_f2[8 * blockIdx.x + 7] = last;
 #endif
     }
-    MAC_F2_STAMP(6);
+    MAC_F2_STAMP(5);
     ts_end(ts);
 }
 

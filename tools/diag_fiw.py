@@ -2,6 +2,8 @@
 (libmaxcover_diag.so; never quote its timings as kernel performance).
 
 MAXCOVER_LIB=.../libmaxcover_diag.so python tools/diag_fiw.py [--config 4] [--disks uniform]
+MAXCOVER_LIB=.../libmaxcover_diag.so python tools/diag_fiw.py --case pairs
+(--case: a layout of tests/fin2_layouts.py; "listed_disks" is what fin2's shared pass took)
 """
 import argparse
 import ctypes
@@ -21,13 +23,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=4)
     ap.add_argument("--disks", default="uniform")
+    ap.add_argument("--case", default=None, help="a layout of tests/fin2_layouts.py")
     args = ap.parse_args()
     pkg = ge.load_package()
     L = pkg.load_library()
     if not hasattr(L, "mac_diag_fiw_read"):
         raise SystemExit("not the diagnostic build (set MAXCOVER_LIB)")
     L.mac_diag_fiw_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64]
-    x, y, w, C, rmax = pkg.workloads.make_config(args.config, disks=args.disks)
+    if args.case:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import fin2_layouts
+        _, (x, y, w), C, rmax, _ = fin2_layouts.geometry(args.case, pkg.workloads)
+    else:
+        x, y, w, C, rmax = pkg.workloads.make_config(args.config, disks=args.disks)
     ctx = pkg.Context(0)
     ctx.set_chain("fused")
     ctx.set_points(x, y, w)
@@ -55,6 +63,8 @@ def main():
            "neighbours_max": int(((info[ok] >> 16) & 0xFFFF).max()),
            "disks_with_neighbours": int((((info[ok] >> 16) & 0xFFFF) > 0).sum()),
            "box_tiles_median": float(np.median((info[ok] & 0xFFFF).astype(np.int64)))}
+    nc = ((info[ok] >> 16) & 0xFFFF).astype(np.int64)
+    out["neighbours_hist"] = {int(v): int((nc == v).sum()) for v in np.unique(nc)}
     hk = np.concatenate([a[:, 1:2], a[:, 12:13], a[:, 15:16], a[:, 13:15], a[:, 2:3]], axis=1).astype(np.int64)[ok]
     hok = (hk > 0).all(axis=1)
     if hok.any():
@@ -76,26 +86,32 @@ def main():
     out["slowest"] = [{"total_us": float((t[q, 6] - t[q, 0]) / 100.0),
                        "phases_us": [round(float(v), 2) for v in ph[q]],
                        "nc": int((info[ok][q] >> 16) & 0xFFFF)} for q in slow]
-    # fin2: per block {start, rows, list, records+entries, decisions, reduction, end}, last-block flag
+    # fin2: per block {start, list (taken while the rows are in flight), rows + records + entries
+    # staged, decisions, reduction, end}, last-block flag
     L.mac_diag_f2_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64]
     nb = 4096
     fb = (ctypes.c_uint64 * (8 * nb))()
     assert L.mac_diag_f2_read(fb, 8 * nb) == 0
     f = np.frombuffer(fb, dtype=np.uint64).reshape(nb, 8).astype(np.int64)
-    f = f[(f[:, 0] > 0) & (f[:, 6] >= f[:, 0])]
+    f = f[(f[:, 0] > 0) & (f[:, 5] >= f[:, 0])]
     f = f[f[:, 0] >= t[:, 0].min()]   # this run's blocks
     if len(f):
-        g = np.maximum.accumulate(np.where(f[:, :7] > 0, f[:, :7], 0), axis=1)
+        g = np.maximum.accumulate(np.where(f[:, :6] > 0, f[:, :6], 0), axis=1)
         ph2 = np.diff(g, axis=1) / 100.0
         last = f[:, 7] == 1
+        # word 6: the listed disks fin2's shared pass took | their entries << 32 (a disk with
+        # neighbours that is not listed decided its shared entries in place)
+        out["listed_disks"] = int(f[0, 6] & 0xFFFFFFFF)
+        out["listed_entries"] = int(f[0, 6] >> 32)
         out["fin2"] = {"blocks": int(len(f)),
-                       "names": ["rows", "list", "records+entries", "decisions", "reduction", "argmin"],
+                       "names": ["list (rows in flight)", "rows+records+entries", "decisions", "reduction",
+                                 "argmin"],
                        "median_us": [round(float(v), 2) for v in np.median(ph2, axis=0)],
                        "max_us": [round(float(v), 2) for v in ph2.max(axis=0)],
                        "last_block_us": [round(float(v), 2) for v in ph2[last][0]] if last.any() else None,
                        "gap_fiw_end_to_first_start_us": float((f[:, 0].min() - t[:, 6].max()) / 100.0),
                        "start_spread_us": float((f[:, 0].max() - f[:, 0].min()) / 100.0),
-                       "span_us": float((f[:, 6].max() - f[:, 0].min()) / 100.0)}
+                       "span_us": float((f[:, 5].max() - f[:, 0].min()) / 100.0)}
     print(json.dumps(out, indent=1))
 
 
