@@ -190,6 +190,50 @@ int32_t mac_poll_basis_f64(mac_ctx* ctx, const double* x_inc, int64_t three_n, c
                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                            double* obj_out, double* best_obj, int64_t* best_idx);
 
+/* ---- swarm constraints on the device (src/TDM_Constraints.jl cons8, cons7) ---------- */
+/* The extreme constraints the reference passes beside cons3 (`cons_ext`, src/FullSimulation.jl:798,
+ * handed to MADS as [cons_ext, cons3] at :86 and :97) that concern the swarm as a whole. A candidate
+ * is infeasible when any constraint that is on rejects it. A NULL mac_cons* means all off. */
+typedef struct mac_cons {
+    double d_sep;   /* cons8 (:157-172): infeasible iff some i != j has
+                       sqrt((x_i-x_j)^2 + (y_i-y_j)^2) < d_sep (fp64, ^2 = x*x, no FMA, correctly
+                       rounded sqrt, strict <; the reference's 15.0). d_sep <= 0 or NaN: off         */
+    double zone_y;  /* cons7 (:142-154): infeasible iff some i has y_i < zone_y && r_i > zone_r      */
+    double zone_r;  /*        (the reference's 200 and 19*tan(FOV/2)). Either NaN: off                */
+} mac_cons;
+/* Non-finite inputs follow the reference's arithmetic: a UAV with a NaN or infinite x or y violates
+ * the spacing with nobody (sqrt(NaN) < d and inf < d are false) and does not disturb the test of the
+ * other UAVs; a NaN y or r never satisfies cons7's comparisons. d_sep = +inf rejects every candidate
+ * with two UAVs at a finite squared distance. N = 1 has no pairs: always feasible under cons8.
+ * cons5 (:106-119, per-UAV target speed) is deliberately not here: it is cons3 with
+ * tan_half_fov = 1, prev = the previous target and d_lim = 2, which the poll calls already take.
+ * The native MADS driver (mac_mads_*, candidates generated on the device) does not take a mac_cons:
+ * only caller-owned polls (the calls below) do.
+ *
+ * mac_cons_mask: one feasibility byte (1 feasible, 0 infeasible) per candidate of the 3N x K
+ * column-major matrix, one kernel launch (k_cons.h: the UAVs counting-sorted by x into cells in LDS,
+ * pairs tested up to d_sep apart in x). N <= 2048 (MAC_E_INVAL above, as mac_area_by_disk_*); three_n % 3 != 0: MAC_E_SIZE; K = 0
+ * writes nothing. The point list is not read: no list need be set. cons = NULL or all off: every
+ * byte 1. The _dev form is stream-ordered and returns after enqueueing. */
+int32_t mac_cons_mask_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                          const mac_cons* cons, uint8_t* feasible_out);
+int32_t mac_cons_mask_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
+                              const mac_cons* cons, uint8_t* d_feasible, void* stream);
+/* mac_poll_best_f64 under a mac_cons: the result of mac_poll_best_f64 on the same candidates with
+ * the objective of every candidate the constraints reject replaced by +inf — the lowest-index
+ * minimiser (ties to the lowest original index), {+inf, -1} when nothing is feasible; obj_out holds
+ * +inf at rejected candidates and at those failing cons3. Three steps on one stream: the mask
+ * launch, the unchanged poll chain, a one-workgroup masked argmin. Rejected candidates ARE evaluated
+ * by the chain and then discarded (the objective is pure, so the result is the same; leaving them out
+ * of the walks would need a mask input to the chain's prep kernels). N <= 2048 when a constraint is
+ * on. cons = NULL or all off: forwards to mac_poll_best_f64 (bit-identical outputs). Threading as
+ * mac_poll_best_f64. */
+int32_t mac_poll_best_cons_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                               const double* r_max, double penalty,
+                               const double* prev, const double* d_lim, double tan_half_fov,
+                               double* obj_out, double* best_obj, int64_t* best_idx,
+                               const mac_cons* cons);
+
 /* ---- native MADS driver ------------------------------------------ */
 /* A granular MADS with a complete LTMADS poll, the restatement of DirectSearch's Optimize!
  * (src/TDM_STATIC_opt.jl:118-169; the third-party algorithm is not vendored, so this is the
@@ -309,6 +353,15 @@ int32_t mac_poll_best_dev_f32(mac_ctx* ctx, const float* d_cands, int64_t three_
                               const double* d_rmax, double penalty,
                               const float* d_prev, const double* d_dlim, double tan_half_fov,
                               int64_t idx_base, double* d_obj, void* d_best, void* stream);
+/* mac_poll_best_dev_f64 under a mac_cons (see mac_poll_best_cons_f64): stream-ordered, no read-back
+ * and no synchronisation. The masked argmin writes d_obj, d_best and d_best's mapped slot as the
+ * plain poll's finalize does, so mac_best_fetch(d_best) returns the constrained result without a
+ * copy. idx_base is added to the index as in the plain call. */
+int32_t mac_poll_best_cons_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
+                                   const double* d_rmax, double penalty,
+                                   const double* d_prev, const double* d_dlim, double tan_half_fov,
+                                   int64_t idx_base, double* d_obj, void* d_best, void* stream,
+                                   const mac_cons* cons);
 /* The host side of one MADS poll step: returns the {objective, index} the latest
  * mac_poll_best_dev_* on d_best wrote. Each d_best buffer gets a mapped host slot that the
  * poll's last finalize block fills (after its d_best stores have reached the device's L2), so

@@ -9,14 +9,15 @@ Gabisanth/MaximumAreaCoverageOptimization.jl. Drop-in replacements for the hot p
 
 Plain `ccall` over the C ABI: no Julia package dependencies. The library path comes from
 ENV["MAXCOVER_LIB"] or defaults to the in-tree build. Not executed in this repository's CI
-(Julia is not installed in the build image); the ctypes mirror
+(Julia is not installed in the build image) — the swarm-constraint wrappers (MacCons, cons_mask,
+poll_best's `cons`) included; the ctypes mirror
 (maximumareacoverageoptimization.jl_amd/_lib.py) makes the same calls with the same arrays and
 is what the parity tests exercise. See INTEGRATION.md.
 =#
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MacCons, cons_mask
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
     joinpath(@__DIR__, "..", "maximumareacoverageoptimization.jl_amd", "libmaxcover.so"))
@@ -149,13 +150,39 @@ function createObjective(cells, N::Integer, r_max::AbstractVector{Float64};
 end
 
 """
-poll_best(cands, r_max; prev, d_lim, tan_half_fov) — one whole MADS poll on the GPU: every
+mac_cons (include/maxcover.h): the swarm constraints a poll applies on the GPU, same layout (24 bytes).
+`d_sep`: cons8's minimum horizontal spacing (src/TDM_Constraints.jl:157-172; 15.0 there; <= 0 or NaN:
+off). `zone_y`, `zone_r`: cons7's altitude zone (:142-154: y < zone_y needs R <= zone_r; 200 and
+19*tan(FOV/2) there; either NaN: off). N <= 2048 UAVs.
+"""
+struct MacCons
+    d_sep::Float64
+    zone_y::Float64
+    zone_r::Float64
+end
+MacCons(; d_sep::Real = NaN, zone_y::Real = NaN, zone_r::Real = NaN) = MacCons(d_sep, zone_y, zone_r)
+
+"""Feasibility (Bool per column) of the 3N x K candidates under `cons`; needs no point list."""
+function cons_mask(cands::Matrix{Float64}, cons::MacCons, ctx::MacContext)
+    K = size(cands, 2)
+    out = Vector{UInt8}(undef, K)
+    check(ccall((:mac_cons_mask_f64, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ref{MacCons}, Ptr{UInt8}),
+                ctx, cands, size(cands, 1), K, Ref(cons), out))
+    return out .!= 0x00
+end
+
+"""
+poll_best(cands, r_max; prev, d_lim, tan_half_fov, cons) — one whole MADS poll on the GPU: every
 candidate's objective, cons3 (src/TDM_Constraints.jl:54-75) as an extreme barrier (+Inf), and
-the lowest-index minimiser. Returns (best_obj, best_idx (1-based, 0 if none feasible), objs).
+the lowest-index minimiser. With `cons::MacCons` (mac_poll_best_cons_f64) the candidates cons8 /
+cons7 reject are +Inf as well (they are still evaluated by the chain, then discarded); `nothing`
+keeps the plain call. Returns (best_obj, best_idx (1-based, 0 if none feasible), objs).
 """
 function poll_best(cands::Matrix{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                    penalty::Float64 = 1e5, prev::Union{Nothing,Vector{Float64}} = nothing,
-                   d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0)
+                   d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
+                   cons::Union{Nothing,MacCons} = nothing)
     K = size(cands, 2)
     objs = Vector{Float64}(undef, K)
     bo = Ref{Float64}(Inf)
@@ -163,13 +190,47 @@ function poll_best(cands::Matrix{Float64}, r_max::Vector{Float64}, ctx::MacConte
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
     GC.@preserve prev d_lim begin
-        check(ccall((:mac_poll_best_f64, libmaxcover), Int32,
-                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
-                     Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ref{Float64}, Ref{Int64}),
-                    ctx, cands, size(cands, 1), K, r_max, penalty, pprev, pdlim, tan_half_fov,
-                    objs, bo, bi))
+        if cons === nothing
+            check(ccall((:mac_poll_best_f64, libmaxcover), Int32,
+                        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
+                         Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ref{Float64}, Ref{Int64}),
+                        ctx, cands, size(cands, 1), K, r_max, penalty, pprev, pdlim, tan_half_fov,
+                        objs, bo, bi))
+        else
+            check(ccall((:mac_poll_best_cons_f64, libmaxcover), Int32,
+                        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
+                         Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ref{Float64}, Ref{Int64},
+                         Ref{MacCons}),
+                        ctx, cands, size(cands, 1), K, r_max, penalty, pprev, pdlim, tan_half_fov,
+                        objs, bo, bi, Ref(cons)))
+        end
     end
     return bo[], bi[] + 1, objs
+end
+
+"""
+The device-pointer forms (mac_cons_mask_dev_f64, mac_poll_best_cons_dev_f64: stream-ordered, no
+read-back) for callers that keep the candidates in HBM (AMDGPU.jl arrays): raw pointers and a
+hipStream_t, as mac_poll_best_dev_f64.
+"""
+function cons_mask_dev(d_cands::Ptr{Float64}, three_n::Integer, K::Integer, cons::MacCons,
+                       d_feasible::Ptr{UInt8}, ctx::MacContext; stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:mac_cons_mask_dev_f64, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ref{MacCons}, Ptr{UInt8}, Ptr{Cvoid}),
+                ctx, d_cands, three_n, K, Ref(cons), d_feasible, stream))
+end
+
+function poll_best_cons_dev(d_cands::Ptr{Float64}, three_n::Integer, K::Integer, d_rmax::Ptr{Float64},
+                            d_best::Ptr{Cvoid}, cons::MacCons, ctx::MacContext; penalty::Float64 = 1e5,
+                            d_prev::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                            d_dlim::Ptr{Float64} = Ptr{Float64}(C_NULL), tan_half_fov::Float64 = 1.0,
+                            idx_base::Integer = 0, d_obj::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                            stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:mac_poll_best_cons_dev_f64, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                 Ptr{Float64}, Float64, Int64, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{MacCons}),
+                ctx, d_cands, three_n, K, d_rmax, penalty, d_prev, d_dlim, tan_half_fov, idx_base,
+                d_obj, d_best, stream, Ref(cons)))
 end
 
 """

@@ -72,6 +72,8 @@ EXPORTS = (
     "mac_mads_best_buffer", "mac_best_reduce_dev", "mac_poll_basis_f64",
     "mac_comm_unique_id", "mac_comm_init", "mac_poll_exchange", "mac_exchange_records",
     "mac_area_by_disk_f64", "mac_area_by_disk_batch_f64", "mac_area_by_disk_dev_f64",
+    "mac_cons_mask_f64", "mac_cons_mask_dev_f64", "mac_poll_best_cons_f64",
+    "mac_poll_best_cons_dev_f64",
 )
 
 
@@ -100,6 +102,29 @@ class FireParams(ctypes.Structure):
                 ("wind_direction", ctypes.c_double), ("ix0", ctypes.c_int64),
                 ("ix1", ctypes.c_int64), ("iy0", ctypes.c_int64), ("iy1", ctypes.c_int64),
                 ("seed", ctypes.c_uint64)]
+
+
+class Cons(ctypes.Structure):
+    """mac_cons (include/maxcover.h): the swarm constraints a poll applies on the device. d_sep:
+    cons8's minimum horizontal spacing (<= 0 or NaN: off); zone_y, zone_r: cons7's altitude zone
+    (y < zone_y needs r <= zone_r; either NaN: off)."""
+    _fields_ = [("d_sep", ctypes.c_double), ("zone_y", ctypes.c_double), ("zone_r", ctypes.c_double)]
+
+
+def make_cons(cons=None, d_sep: float | None = None, zone_y: float | None = None,
+              zone_r: float | None = None) -> Cons | None:
+    """A Cons from a Cons, a mapping / object with d_sep, zone_y, zone_r fields (missing: off), or
+    the keyword values; None stays None (all constraints off)."""
+    if isinstance(cons, Cons):
+        return cons
+    if cons is not None:
+        get = cons.get if hasattr(cons, "get") else lambda k, d=None: getattr(cons, k, d)
+        d_sep, zone_y, zone_r = get("d_sep"), get("zone_y"), get("zone_r")
+    elif d_sep is None and zone_y is None and zone_r is None:
+        return None
+    nan = float("nan")
+    return Cons(nan if d_sep is None else float(d_sep), nan if zone_y is None else float(zone_y),
+                nan if zone_r is None else float(zone_r))
 
 
 class MaxCoverError(RuntimeError):
@@ -152,6 +177,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_area_by_disk_dev_f64": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _i32),
         "mac_poll_best_dev_f64": ([_vp, _vp, _i64, _i64, _vp, ctypes.c_double, _vp, _vp,
                                    ctypes.c_double, _i64, _vp, _vp, _vp], _i32),
+        "mac_cons_mask_f64": ([_vp, _dp, _i64, _i64, ctypes.POINTER(Cons), _u8p], _i32),
+        "mac_cons_mask_dev_f64": ([_vp, _vp, _i64, _i64, ctypes.POINTER(Cons), _vp, _vp], _i32),
+        "mac_poll_best_cons_f64": ([_vp, _dp, _i64, _i64, _dp, ctypes.c_double, _dp, _dp,
+                                    ctypes.c_double, _dp, _dp, _i64p, ctypes.POINTER(Cons)], _i32),
+        "mac_poll_best_cons_dev_f64": ([_vp, _vp, _i64, _i64, _vp, ctypes.c_double, _vp, _vp,
+                                        ctypes.c_double, _i64, _vp, _vp, _vp,
+                                        ctypes.POINTER(Cons)], _i32),
         "mac_best_fetch": ([_vp, _vp, _vp, _dp, _i64p], _i32),
         "mac_best_reduce_dev": ([_vp, _vp, _i32, _vp, _vp], _i32),
         "mac_comm_unique_id": ([ctypes.c_char_p, _vp], _i32),
@@ -549,9 +581,32 @@ class Context:
                                                float(penalty), _ptr(out)))
         return out
 
+    def cons_mask(self, cands, cons) -> np.ndarray:
+        """mac_cons_mask_f64: the feasibility of each candidate (K x 3N rows) under ``cons`` (a Cons,
+        or anything make_cons takes; None: all feasible), as a bool array. No point list needed."""
+        c = _f64(cands)
+        if c.ndim != 2:
+            raise ValueError("cands must be K x 3N")
+        K, three_n = c.shape
+        out = np.zeros(max(K, 1), dtype=np.uint8)
+        cs = make_cons(cons)
+        _check(self._L.mac_cons_mask_f64(self._h, _ptr(c), three_n, K,
+                                         ctypes.byref(cs) if cs is not None else None,
+                                         out.ctypes.data_as(_u8p)))
+        return out[:K].astype(bool)
+
+    def cons_mask_dev(self, d_cands, three_n: int, K: int, cons, d_feasible, stream=None) -> None:
+        """mac_cons_mask_dev_f64: device pointers (d_feasible: K uint8), ordered on ``stream``."""
+        cs = make_cons(cons)
+        _check(self._L.mac_cons_mask_dev_f64(self._h, _devptr(d_cands), int(three_n), int(K),
+                                             ctypes.byref(cs) if cs is not None else None,
+                                             _devptr(d_feasible), _stream(stream, self.device)))
+
     def poll_best(self, cands, r_max, penalty: float = 1e5, prev=None, d_lim=None,
-                  tan_half_fov: float = 1.0, want_all: bool = False):
-        """Returns (best_obj, best_idx[, objectives]); best_idx = -1 if none feasible."""
+                  tan_half_fov: float = 1.0, want_all: bool = False, cons=None):
+        """Returns (best_obj, best_idx[, objectives]); best_idx = -1 if none feasible. ``cons`` (a
+        Cons, or anything make_cons takes): the swarm constraints applied on the device
+        (mac_poll_best_cons_f64); None keeps the plain call."""
         c = _f64(cands)
         K, three_n = c.shape
         rm = _f64(r_max)
@@ -560,11 +615,15 @@ class Context:
         objs = np.empty(K) if want_all else None
         bo = ctypes.c_double()
         bi = _i64()
-        _check(self._L.mac_poll_best_f64(
-            self._h, _ptr(c), three_n, K, _ptr(rm), float(penalty),
-            _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
-            float(tan_half_fov), _ptr(objs) if objs is not None else None,
-            ctypes.byref(bo), ctypes.byref(bi)))
+        args = (self._h, _ptr(c), three_n, K, _ptr(rm), float(penalty),
+                _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
+                float(tan_half_fov), _ptr(objs) if objs is not None else None,
+                ctypes.byref(bo), ctypes.byref(bi))
+        if cons is None:
+            _check(self._L.mac_poll_best_f64(*args))
+        else:
+            cs = make_cons(cons)
+            _check(self._L.mac_poll_best_cons_f64(*args, ctypes.byref(cs)))
         if want_all:
             return bo.value, int(bi.value), objs
         return bo.value, int(bi.value)
@@ -685,11 +744,17 @@ class Context:
 
     def poll_best_dev(self, d_cands, three_n: int, K: int, d_rmax, d_best, penalty: float = 1e5,
                       d_prev=None, d_dlim=None, tan_half_fov: float = 1.0, idx_base: int = 0,
-                      d_obj=None, stream=None) -> None:
-        _check(self._L.mac_poll_best_dev_f64(
-            self._h, _devptr(d_cands), int(three_n), int(K), _devptr(d_rmax), float(penalty),
-            _devptr(d_prev), _devptr(d_dlim), float(tan_half_fov), int(idx_base),
-            _devptr(d_obj), _devptr(d_best), _stream(stream, self.device)))
+                      d_obj=None, stream=None, cons=None) -> None:
+        """mac_poll_best_dev_f64; with ``cons`` (a Cons, or anything make_cons takes) the masked poll
+        mac_poll_best_cons_dev_f64 (stream-ordered as well; best_fetch(d_best) reads its result)."""
+        args = (self._h, _devptr(d_cands), int(three_n), int(K), _devptr(d_rmax), float(penalty),
+                _devptr(d_prev), _devptr(d_dlim), float(tan_half_fov), int(idx_base),
+                _devptr(d_obj), _devptr(d_best), _stream(stream, self.device))
+        if cons is None:
+            _check(self._L.mac_poll_best_dev_f64(*args))
+        else:
+            cs = make_cons(cons)
+            _check(self._L.mac_poll_best_cons_dev_f64(*args, ctypes.byref(cs)))
 
     def poll_step(self, d_cands, three_n: int, K: int, d_rmax, d_best, penalty: float = 1e5,
                   d_prev=None, d_dlim=None, tan_half_fov: float = 1.0, idx_base: int = 0,

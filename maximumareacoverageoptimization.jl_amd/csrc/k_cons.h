@@ -1,0 +1,298 @@
+// k_cons.h — the swarm constraints of src/TDM_Constraints.jl evaluated on the device, one
+// feasibility byte per candidate (mac_cons, include/maxcover.h), and the masked poll argmin.
+//
+//   cons8 (:157-172)  infeasible iff some i != j has sqrt((x_i-x_j)^2 + (y_i-y_j)^2) < d_sep
+//   cons7 (:142-154)  infeasible iff some i has y_i < zone_y && r_i > zone_r
+//
+// cons8's pair test is the coverage predicate (predicate.h): with a = fl(fl(dx*dx) + fl(dy*dy)),
+// fl(sqrt a) < d  <=>  a <= T(d). dx = fl(x_i - x_j) and fl(x_j - x_i) differ in sign only (rounding
+// to nearest is symmetric), so a is the same for (i, j) and (j, i) and every unordered pair is
+// tested once. A UAV with a NaN or infinite x or y has a = inf or NaN against every other UAV
+// (dx or dy is inf or NaN, and nothing finite cancels it), and neither satisfies a <= T for any T
+// (T <= DBL_MAX): it violates with nobody and is left out of the pair tests.
+//
+// The cull. A pair with |fl(x_j - x_i)| >= dcut is skipped without its fp64 test. Claim: with
+// dcut = d_sep every skipped pair is feasible, provided D2 := fl(d_sep * d_sep) > T(d_sep) — which the
+// host checks for the d_sep at hand (cons_args below; it holds for every d_sep whose square neither
+// overflows nor loses bits to the subnormal range, because sqrt(fl(d*d)) rounds back to d in binary
+// floating point; it fails e.g. for d_sep = 1e-200, where D2 = 0 <= T, and the host then passes
+// dcut = +inf, which only skips dx = +-inf, i.e. a = inf: feasible).
+//   1. dx := fl(x_j - x_i), |dx| >= d_sep > 0 (possibly inf by overflow), so as reals
+//      dx*dx >= d_sep*d_sep, and by monotone rounding fl(dx*dx) >= D2.
+//   2. dy is finite or +-inf (both y finite), so fl(dy*dy) >= 0 and is not NaN; hence
+//      fl(dx*dx) + fl(dy*dy) >= fl(dx*dx) as extended reals, and a = fl(of that sum) >=
+//      fl(dx*dx) >= D2 (rounding is monotone and leaves the double fl(dx*dx) fixed).
+//   3. a >= D2 > T  =>  not (a <= T)  =>  not (fl(sqrt a) < d_sep): the pair is feasible.
+// Whole runs of pairs are skipped the same way. The finite UAVs are counting-sorted in LDS into
+// kConsCells cells along x with boundaries bnd[0] = min x <= bnd[1] <= ... (doubles, non-decreasing);
+// a UAV's cell g is guessed by a division and then corrected against the boundaries themselves until
+// bnd[g] <= x (and x < bnd[g + 1] unless g is the last cell), so that inequality holds exactly and
+// does not depend on how the guess rounded. The sorted positions are ordered by cell (in any order
+// inside a cell). The UAV at position p (x_i) is tested against the positions q > p, and stops at the
+// first later cell c with fl(bnd[c] - x_i) >= dcut: every position from there on has
+// x_j >= bnd[its cell] >= bnd[c], subtraction rounds monotonically, so fl(x_j - x_i) >=
+// fl(bnd[c] - x_i) >= dcut and the pair is feasible by 1-3. Every unordered pair of finite UAVs is
+// thus either tested (from its lower position) or proven feasible. Cells are at least dcut wide, so a
+// UAV meets its own cell and the next one or two; with dcut = +inf all UAVs share cell 0 and every
+// pair is tested. No finite UAV is lost: each takes one slot of its cell from an atomic cursor. The
+// order inside a cell depends on the atomics; the result, an OR over pairs, does not.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "predicate.h"
+#include "k_common.h"
+#include "k_final.h"
+
+#pragma clang fp contract(off)
+
+namespace mac {
+
+constexpr int kConsMaxN = 2048;     // UAVs sorted in LDS: x and y, 16 B each (dynamic LDS, 32 KB)
+constexpr int kConsBlock = 256;
+constexpr int kConsCells = 256;     // cells of the counting sort by x (one per thread)
+constexpr int kConsArgminBlock = 1024;
+
+struct ConsArgs {
+    double T;        // cover_threshold(d_sep): the pair is infeasible iff a <= T
+    double dcut;     // the sweep's cut: d_sep when fl(d_sep*d_sep) > T, else +inf (see above)
+    double zone_y;   // cons7
+    double zone_r;
+    int sep;         // cons8 on (d_sep > 0)
+    int zone;        // cons7 on (neither field NaN)
+};
+
+// Elements per thread of the sort: the sorted array holds P = 256 S >= N entries (S = 1, 2, 4, 8).
+static inline int cons_slots(int N)
+{
+    int S = 1;
+    while (kConsBlock * S < N) S <<= 1;
+    return S;
+}
+
+static inline ConsArgs cons_args(double d_sep, double zone_y, double zone_r)
+{
+    ConsArgs a;
+    a.sep = d_sep > 0.0 ? 1 : 0;   // (NaN: off)
+    a.T = cover_threshold(d_sep);
+    const double d2 = d_sep * d_sep;
+    a.dcut = (a.sep && d2 > a.T) ? d_sep : __builtin_inf();
+    a.zone = (zone_y == zone_y && zone_r == zone_r) ? 1 : 0;
+    a.zone_y = zone_y;
+    a.zone_r = zone_r;
+    return a;
+}
+
+// Workgroup = candidate (column k of the 3N x K matrix). Thread t loads elements s * 256 + t (s < S,
+// 256 S >= N) and owns cell t of the kConsCells cells. Dynamic LDS: 17 * 256 S bytes (x, y and the
+// cell of every sorted position).
+template <int S>
+__global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __restrict__ cands, int N,
+                                                             ConsArgs a, uint8_t* __restrict__ feasible)
+{
+    static_assert(kConsCells == kConsBlock, "one cell per thread");
+    constexpr int P = kConsBlock * S;
+    extern __shared__ double cons_lds[];
+    double* const sx = cons_lds;
+    double* const sy = cons_lds + P;
+    unsigned char* const sc = reinterpret_cast<unsigned char*>(cons_lds + 2 * P);
+    __shared__ double bnd[kConsCells];          // cell c holds the x with bnd[c] <= x (< bnd[c + 1])
+    __shared__ int cnt[kConsCells];             // per cell: its count, then its fill cursor
+    __shared__ int start[kConsCells + 1];       // first sorted position of each cell; [cells]: the total
+    __shared__ double wmin[kConsBlock / kWave], wmax[kConsBlock / kWave];
+    __shared__ int wsum[kConsBlock / kWave];
+    __shared__ int viol;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const double* __restrict__ c = cands + (size_t)blockIdx.x * (size_t)(3 * N);
+    const double inf = __builtin_inf();
+    if (tid == 0) viol = 0;
+    cnt[tid] = 0;
+    double kx[S], ky[S];
+    bool bad = false;
+    double lo = inf, hi = -inf;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const int e = s * kConsBlock + tid;
+        kx[s] = inf;   // +inf: not a UAV of the pair tests (past N, or a non-finite coordinate)
+        ky[s] = 0.0;
+        if (e < N) {
+            const double x = c[e], y = c[N + e], r = c[2 * N + e];
+            bad |= a.zone && y < a.zone_y && r > a.zone_r;
+            if (__builtin_fabs(x) < inf && __builtin_fabs(y) < inf) {
+                kx[s] = x;
+                ky[s] = y;
+                lo = x < lo ? x : lo;
+                hi = x > hi ? x : hi;
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double l2 = __shfl_xor(lo, off, kWave), h2 = __shfl_xor(hi, off, kWave);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) {
+        wmin[wave] = lo;
+        wmax[wave] = hi;
+    }
+    __syncthreads();   // (viol = 0 and cnt = 0 are visible from here on)
+    if (bad) viol = 1;
+#pragma unroll
+    for (int q = 0; q < kConsBlock / kWave; ++q) {
+        lo = wmin[q] < lo ? wmin[q] : lo;
+        hi = wmax[q] > hi ? wmax[q] : hi;
+    }
+    // cells of width w >= dcut over [lo, hi]; bnd is non-decreasing in the cell index (the product
+    // and the sum round monotonically), bnd[0] = lo. w = +inf (no cut, or an overflowing extent)
+    // puts every UAV into cell 0: all pairs are tested.
+    const double ext = (hi - lo) / (double)kConsCells;
+    const double w = a.dcut > ext ? a.dcut : ext;
+    const double invw = 1.0 / w;
+    bnd[tid] = tid == 0 ? lo : lo + (double)tid * w;
+    __syncthreads();
+    const bool sweep = a.sep && N > 1 && !viol && lo < inf;   // workgroup-uniform
+    if (sweep) {
+        // each UAV's cell: a guess from the division, then corrected against the boundaries
+        // themselves, so that bnd[g] <= x holds exactly, whatever the guess was
+        int g[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            g[s] = -1;
+            if (kx[s] < inf) {
+                const double u = (kx[s] - lo) * invw;
+                int q = u >= (double)(kConsCells - 1) ? kConsCells - 1 : u > 0.0 ? (int)u : 0;
+                while (q > 0 && kx[s] < bnd[q]) --q;
+                while (q < kConsCells - 1 && kx[s] >= bnd[q + 1]) ++q;
+                g[s] = q;
+                atomicAdd(&cnt[q], 1);
+            }
+        }
+        __syncthreads();
+        // exclusive scan of the counts: start[c]
+        const int mine = cnt[tid];
+        int incl = mine;
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const int v = __shfl_up(incl, off, kWave);
+            if (lane >= off) incl += v;
+        }
+        if (lane == kWave - 1) wsum[wave] = incl;
+        __syncthreads();
+        int base = 0, total = 0;
+#pragma unroll
+        for (int q = 0; q < kConsBlock / kWave; ++q) {
+            base += q < wave ? wsum[q] : 0;
+            total += wsum[q];
+        }
+        start[tid] = base + incl - mine;
+        cnt[tid] = base + incl - mine;   // the cell's fill cursor
+        if (tid == 0) start[kConsCells] = total;
+        __syncthreads();
+        // counting sort: every finite UAV takes one slot of its cell (their order inside a cell
+        // depends on the atomics' order; the result, an OR over pairs, does not)
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (g[s] >= 0) {
+                const int pos = atomicAdd(&cnt[g[s]], 1);
+                sx[pos] = kx[s];
+                sy[pos] = ky[s];
+                sc[pos] = (unsigned char)g[s];
+            }
+        }
+        __syncthreads();
+        const int nv = start[kConsCells];
+        volatile int* const vflag = &viol;
+        for (int p = tid; p < nv; p += kConsBlock) {
+            if (*vflag) break;   // another thread found a violation: the candidate is decided
+            const double xi = sx[p], yi = sy[p];
+            int cell = sc[p];
+            for (int q = p + 1; q < nv; ++q) {
+                const int cq = sc[q];
+                if (cq != cell) {   // a later cell: everything from here on has x >= bnd[cq]
+                    if (bnd[cq] - xi >= a.dcut) break;
+                    cell = cq;
+                }
+                const double dx = sx[q] - xi;
+                if (__builtin_fabs(dx) >= a.dcut) continue;
+                const double dy = sy[q] - yi;
+                if (dx * dx + dy * dy <= a.T) {
+                    *vflag = 1;
+                    break;
+                }
+                if ((q & 63) == 0 && *vflag) break;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) feasible[blockIdx.x] = viol ? 0 : 1;
+}
+
+// The masked poll's last launch, one workgroup: obj[k] <- +inf where feasible[k] == 0 (in place),
+// then the lexicographic (objective, index) minimum over the candidates with an objective < +inf
+// (finalize_argmin's rule, k_final.h: NaN and +inf never win, ties to the lowest index; none:
+// {+inf, -1}), written to best and to its mapped host slot exactly as best_reduce_kernel does.
+__global__ __launch_bounds__(kConsArgminBlock) void cons_argmin_kernel(double* __restrict__ obj,
+                                                                     const uint8_t* __restrict__ feasible,
+                                                                     int64_t K, int64_t idx_base,
+                                                                     unsigned long long* best, uint64_t* mirror,
+                                                                     uint64_t seq)
+{
+    __shared__ double wv[kConsArgminBlock / kWave];
+    __shared__ long long wi[kConsArgminBlock / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const double inf = __builtin_inf();
+    double bv = inf;
+    long long bi = -1;
+    auto take = [&](double o, long long i) {
+        if (i >= 0 && (bi < 0 || o < bv || (o == bv && i < bi))) {
+            bv = o;
+            bi = i;
+        }
+    };
+    for (int64_t k = tid; k < K; k += kConsArgminBlock) {
+        double o = obj[k];
+        if (!feasible[k]) {
+            o = inf;
+            obj[k] = inf;
+        }
+        if (o < inf) take(o, (long long)k);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o = __shfl_xor(bv, off, kWave);
+        const long long i = __shfl_xor(bi, off, kWave);
+        take(o, i);
+    }
+    if (lane == 0) {
+        wv[wave] = bv;
+        wi[wave] = bi;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    bv = lane < kConsArgminBlock / kWave ? wv[lane] : inf;
+    bi = lane < kConsArgminBlock / kWave ? wi[lane] : -1;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o = __shfl_xor(bv, off, kWave);
+        const long long i = __shfl_xor(bi, off, kWave);
+        take(o, i);
+    }
+    if (lane == 0) {
+        const bool none = bi < 0;
+        const uint64_t o = __builtin_bit_cast(uint64_t, none ? inf : bv);
+        const uint64_t ix = (uint64_t)(none ? (long long)-1 : (long long)idx_base + bi);
+        __hip_atomic_store(best, (unsigned long long)o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(best + 1, (unsigned long long)ix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (mirror) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            mirror[0] = o;
+            mirror[1] = ix;
+            mirror[2] = seq;
+            mirror[3] = mirror_check(o, ix, seq);
+        }
+    }
+}
+
+}  // namespace mac

@@ -28,6 +28,9 @@
 //   closure_kernel        one candidate in one launch (the per-trial-point objective callback)
 //   by_disk_kernel        the same launch shape keeping the per-disk values: the weight each disk
 //                         owns (first covering disk in index order) and the weight it alone covers
+//   cons_mask_kernel      the swarm constraints (minimum spacing cons8, altitude zone cons7), one
+//                         feasibility byte per candidate: UAVs counting-sorted by x into cells in LDS,
+//                         pairs tested up to the spacing apart; cons_argmin_kernel: the masked poll's argmin (k_cons.h)
 // (Cross-workgroup hand-offs use agent-scope stores drained before one counter add, never a
 // device-scope fence: that fence writes back the XCD's L2 on gfx950.)
 // An entry is credited to the LOWEST-index disk covering it (exactly-once union count), so the
@@ -45,3 +48,4 @@
 #include "k_closure.h"
 #include "k_bydisk.h"
 #include "k_fiw.h"
+#include "k_cons.h"

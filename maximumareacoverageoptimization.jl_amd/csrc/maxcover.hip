@@ -172,6 +172,7 @@ struct Lane {
     DevBuf cpart, carrive, ctot;               // closure_kernel: credits, arrivals, packed count
     DevBuf clv;                                // closure candidates written by the host (BAR)
     DevBuf bdpart, bdarrive, bdout;            // by_disk_kernel: owned words, arrivals; host calls' results
+    DevBuf cmask, cbest;                       // masked poll (k_cons.h): feasibility bytes; the chain's own best
     DevBuf prec, cost;                         // prep launch: per-disk records; walk costs
     int um_hist[8] = {};                       // most distinct positions of a disk, last 8 polls
     int walk_hist[8] = {};                     // the walk AUTO would have chosen, last 8 polls
@@ -1240,11 +1241,49 @@ static void staged_upload(const void* src, void* pinned, void* dev, size_t bytes
     if (err.e != hipSuccess) throw err;
 }
 
+// ---- swarm constraints (k_cons.h): the mask launch and the masked poll's argmin
+
+// The kernel's arguments from a mac_cons; false when every constraint is off (or cons is null).
+static bool cons_active(const mac_cons* cons, ConsArgs* a)
+{
+    if (!cons) return false;
+    *a = cons_args(cons->d_sep, cons->zone_y, cons->zone_r);
+    return a->sep || a->zone;
+}
+
+static void cons_mask_enqueue(hipStream_t s, const double* d_cands, int N, int64_t K, const ConsArgs& a,
+                              uint8_t* d_feas)
+{
+    constexpr int64_t kMaxWG = (int64_t)1 << 23;   // workgroups per launch (2^31 threads)
+    const int S = cons_slots(N);                   // UAVs per thread: 1, 2, 4, 8 (N <= 2048)
+    void (*const kern)(const double*, int, ConsArgs, uint8_t*) =
+        S == 1 ? cons_mask_kernel<1> : S == 2 ? cons_mask_kernel<2> : S == 4 ? cons_mask_kernel<4> : cons_mask_kernel<8>;
+    const uint32_t lds = (uint32_t)(17 * kConsBlock * S);   // x, y, cell per sorted position
+    for (int64_t k0 = 0; k0 < K; k0 += kMaxWG) {
+        const int64_t B = std::min(kMaxWG, K - k0);
+        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kConsBlock), lds, s,
+                           d_cands + (size_t)k0 * (size_t)(3 * N), N, a, d_feas + k0);
+        HCK(hipGetLastError());
+    }
+}
+
+// obj[k] <- +inf at masked candidates, the argmin of the rest into best (and its mapped slot).
+static void cons_argmin_enqueue(hipStream_t s, double* d_obj, const uint8_t* d_feas, int64_t K, int64_t idx_base,
+                                void* d_best, uint64_t* d_mirror, uint64_t seq)
+{
+    hipLaunchKernelGGL(cons_argmin_kernel, dim3(1), dim3(kConsArgminBlock), 0, s, d_obj, d_feas, K, idx_base,
+                       (unsigned long long*)d_best, d_mirror, seq);
+    HCK(hipGetLastError());
+}
+
+// cons (masked poll, mac_poll_best_cons_f64; needs best_obj / best_idx): the mask launch before the
+// chain, the masked argmin after it, in place on the lane's objectives and best.
 template <class T>
 static int32_t host_eval(mac_ctx* ctx, const T* cands, int64_t three_n, int64_t K,
                          const double* r_max, double penalty, const T* prev,
                          const double* d_lim, double tan_half_fov, double* area_out,
-                         double* obj_out, double* best_obj, int64_t* best_idx)
+                         double* obj_out, double* best_obj, int64_t* best_idx,
+                         const ConsArgs* cons = nullptr)
 {
     constexpr bool f32 = std::is_same<T, float>::value;
     int32_t rc = check_common(ctx, three_n, K);
@@ -1320,11 +1359,17 @@ static int32_t host_eval(mac_ctx* ctx, const T* cands, int64_t three_n, int64_t 
         }
     }
     const bool tiled = use_tiled(ctx, N, hc, three_n);
+    if (cons) {
+        L->cmask.reserve((size_t)K);
+        cons_mask_enqueue(s, L->cands.as<double>(), N, K, *cons, L->cmask.as<uint8_t>());
+    }
     enqueue_eval(ctx, L, s, matrix_src(L->cands.as<double>(), N), N, (int)K, tiled, d_rmax, penalty, d_prev,
                  d_dlimT, d_prev ? L->dlimraw.as<double>() : nullptr, tan_half_fov,
                  area_out ? L->area.as<double>() : nullptr,
                  want_obj ? L->obj.as<double>() : nullptr,
                  (best_obj || best_idx) ? L->best.as<double>() : nullptr, 0);
+    if (cons)
+        cons_argmin_enqueue(s, L->obj.as<double>(), L->cmask.as<uint8_t>(), K, 0, L->best.p, nullptr, 0);
     // results: into the pinned buffer (the upload has completed before the kernels ran), then
     // one host copy each after the sync
     double* ho = staged ? (double*)L->h_io.p : nullptr;
@@ -1751,7 +1796,7 @@ void mac_ctx_destroy(mac_ctx* ctx)
                           &l->lanexp, &l->rows, &l->nboxT, &l->cnt, &l->dlimraw, &l->finblk, &l->finarrive, &l->c32, &l->p32,
                           &l->cpart, &l->carrive, &l->ctot, &l->clv, &l->prec, &l->cost, &l->nboxU,
                           &l->ncountU, &l->orjobs, &l->pd, &l->dead8, &l->frows, &l->fwhint, &l->fwlist, &l->fwcount,
-                          &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout})
+                          &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout, &l->cmask, &l->cbest})
             b->release();
         if (l->done) (void)hipEventDestroy(l->done);
 
@@ -3520,7 +3565,7 @@ template <class T>
 static int32_t poll_best_dev(mac_ctx* ctx, const T* d_cands_in, int64_t three_n, int64_t K,
                              const double* d_rmax, double penalty, const T* d_prev_in,
                              const double* d_dlim, double tan_half_fov, int64_t idx_base,
-                             double* d_obj, void* d_best, void* stream)
+                             double* d_obj, void* d_best, void* stream, const ConsArgs* cons = nullptr)
 {
     if (ctx && ctx->host_stats) t_poll_entry = std::chrono::steady_clock::now();
     constexpr bool f32 = std::is_same<T, float>::value;
@@ -3575,6 +3620,17 @@ static int32_t poll_best_dev(mac_ctx* ctx, const T* d_cands_in, int64_t three_n,
     }
     uint64_t seq = 0;
     uint64_t* d_mirror = assign_mirror(ctx, d_best, &seq);
+    if (cons) {
+        // the masked poll (mac_poll_best_cons_dev_f64): the mask, the chain unchanged into the lane's
+        // own best (no slot), then the masked argmin into d_o (in place), d_best and its slot
+        L->cmask.reserve((size_t)K);
+        L->cbest.reserve(16);
+        cons_mask_enqueue(s, d_cands, N, K, *cons, L->cmask.as<uint8_t>());
+        enqueue_eval(ctx, L, s, matrix_src(d_cands, N), N, (int)K, use_tiled(ctx, N, nullptr, three_n), d_rmax,
+                     penalty, d_prev, d_dlimT, d_dlim, tan_half_fov, nullptr, d_o, L->cbest.as<double>(), 0);
+        cons_argmin_enqueue(s, d_o, L->cmask.as<uint8_t>(), K, idx_base, d_best, d_mirror, seq);
+        return MAC_OK;
+    }
     enqueue_eval(ctx, L, s, matrix_src(d_cands, N), N, (int)K, use_tiled(ctx, N, nullptr, three_n), d_rmax,
                  penalty, d_prev, d_dlimT, d_dlim, tan_half_fov, nullptr, d_o, (double*)d_best, idx_base,
                  d_mirror, seq);
@@ -3699,6 +3755,125 @@ int32_t mac_poll_best_dev_f32(mac_ctx* ctx, const float* d_cands, int64_t three_
     ABI_BEGIN
     return poll_best_dev<float>(ctx, d_cands, three_n, K, d_rmax, penalty, d_prev, d_dlim,
                                 tan_half_fov, idx_base, d_obj, d_best, stream);
+    ABI_END
+}
+
+// ---- swarm constraints (k_cons.h; include/maxcover.h mac_cons)
+
+// The mask calls' argument checks. The point list is not read: no MAC_E_NOPOINTS.
+static int32_t cons_check(mac_ctx* ctx, const void* cands, int64_t three_n, int64_t K, const void* out)
+{
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (three_n < 0 || K < 0) return fail(MAC_E_INVAL, "negative size");
+    if (three_n % 3 != 0)
+        return fail(MAC_E_SIZE, "InexactError: Int64(" + std::to_string(three_n) + "/3)");
+    if (three_n / 3 > kConsMaxN)
+        return fail(MAC_E_INVAL, "mac_cons: N = " + std::to_string(three_n / 3) + " > " + std::to_string(kConsMaxN) +
+                                     " UAVs (the constraint kernel's limit)");
+    if (K > (int64_t)1 << 30) return fail(MAC_E_INVAL, "K too large");
+    if (K == 0) return MAC_OK;
+    if (!cands && three_n > 0) return fail(MAC_E_INVAL, "null candidates");
+    if (!out) return fail(MAC_E_INVAL, "null feasibility output");
+    return MAC_OK;
+}
+
+int32_t mac_cons_mask_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K, const mac_cons* cons,
+                          uint8_t* feasible_out)
+{
+    ABI_BEGIN
+    int32_t rc = cons_check(ctx, cands, three_n, K, feasible_out);
+    if (rc || K == 0) return rc;
+    ConsArgs a;
+    if (!cons_active(cons, &a) || three_n == 0) {   // nothing on, or no UAV to violate anything
+        std::memset(feasible_out, 1, (size_t)K);
+        return MAC_OK;
+    }
+    const int N = (int)(three_n / 3);
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t in_bytes = sizeof(double) * (size_t)three_n * (size_t)K;
+    L->cands.reserve(in_bytes);
+    L->cmask.reserve((size_t)K);
+    const bool staged = in_bytes <= ((size_t)64 << 20);
+    if (staged) {
+        L->h_io.reserve(std::max<size_t>(in_bytes, 64));
+        staged_upload(cands, L->h_io.p, L->cands.p, in_bytes, s);
+    } else {
+        HCK(hipMemcpyAsync(L->cands.p, cands, in_bytes, hipMemcpyHostToDevice, s));
+    }
+    cons_mask_enqueue(s, L->cands.as<double>(), N, K, a, L->cmask.as<uint8_t>());
+    if (staged && (size_t)K <= L->h_io.cap) {   // (the upload has completed before the kernel ran)
+        HCK(hipMemcpyAsync(L->h_io.p, L->cmask.p, (size_t)K, hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+        std::memcpy(feasible_out, L->h_io.p, (size_t)K);
+    } else {
+        HCK(hipMemcpyAsync(feasible_out, L->cmask.p, (size_t)K, hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+    }
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_cons_mask_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
+                              const mac_cons* cons, uint8_t* d_feasible, void* stream)
+{
+    ABI_BEGIN
+    int32_t rc = cons_check(ctx, d_cands, three_n, K, d_feasible);
+    if (rc || K == 0) return rc;
+    set_device(ctx);
+    hipStream_t s = (hipStream_t)stream;   // NULL: HIP's null stream
+    ConsArgs a;
+    if (!cons_active(cons, &a) || three_n == 0) {
+        HCK(hipMemsetAsync(d_feasible, 1, (size_t)K, s));
+        return MAC_OK;
+    }
+    cons_mask_enqueue(s, d_cands, (int)(three_n / 3), K, a, d_feasible);
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_poll_best_cons_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                               const double* r_max, double penalty, const double* prev,
+                               const double* d_lim, double tan_half_fov, double* obj_out,
+                               double* best_obj, int64_t* best_idx, const mac_cons* cons)
+{
+    ConsArgs a;
+    if (!cons_active(cons, &a))   // nothing on: the plain call, untouched
+        return mac_poll_best_f64(ctx, cands, three_n, K, r_max, penalty, prev, d_lim, tan_half_fov, obj_out,
+                                 best_obj, best_idx);
+    ABI_BEGIN
+    if (!best_obj || !best_idx) return fail(MAC_E_INVAL, "null best output");
+    if (!r_max && three_n > 0) return fail(MAC_E_INVAL, "null r_max");
+    int32_t rc = check_common(ctx, three_n, K);
+    if (rc) return rc;
+    if (three_n / 3 > kConsMaxN)
+        return fail(MAC_E_INVAL, "mac_poll_best_cons: N = " + std::to_string(three_n / 3) + " > " +
+                                     std::to_string(kConsMaxN) + " UAVs (the constraint kernel's limit)");
+    return host_eval<double>(ctx, cands, three_n, K, r_max, penalty, prev, d_lim, tan_half_fov, nullptr,
+                             obj_out, best_obj, best_idx, &a);
+    ABI_END
+}
+
+int32_t mac_poll_best_cons_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three_n, int64_t K,
+                                   const double* d_rmax, double penalty, const double* d_prev,
+                                   const double* d_dlim, double tan_half_fov, int64_t idx_base,
+                                   double* d_obj, void* d_best, void* stream, const mac_cons* cons)
+{
+    ConsArgs a;
+    if (!cons_active(cons, &a) || K == 0)   // nothing on (or nothing to mask): the plain call, untouched
+        return mac_poll_best_dev_f64(ctx, d_cands, three_n, K, d_rmax, penalty, d_prev, d_dlim, tan_half_fov,
+                                     idx_base, d_obj, d_best, stream);
+    ABI_BEGIN
+    int32_t rc = poll_dev_check(ctx, d_cands, three_n, K, d_prev, d_dlim, d_best);
+    if (rc) return rc;
+    if (three_n / 3 > kConsMaxN)
+        return fail(MAC_E_INVAL, "mac_poll_best_cons_dev: N = " + std::to_string(three_n / 3) + " > " +
+                                     std::to_string(kConsMaxN) + " UAVs (the constraint kernel's limit)");
+    if ((uintptr_t)d_best & 7) return fail(MAC_E_INVAL, "d_best not 8-byte aligned");
+    return poll_best_dev<double>(ctx, d_cands, three_n, K, d_rmax, penalty, d_prev, d_dlim, tan_half_fov,
+                                 idx_base, d_obj, d_best, stream, &a);
     ABI_END
 }
 
