@@ -207,8 +207,8 @@ typedef struct mac_cons {
  * with two UAVs at a finite squared distance. N = 1 has no pairs: always feasible under cons8.
  * cons5 (:106-119, per-UAV target speed) is deliberately not here: it is cons3 with
  * tan_half_fov = 1, prev = the previous target and d_lim = 2, which the poll calls already take.
- * The native MADS driver (mac_mads_*, candidates generated on the device) does not take a mac_cons:
- * only caller-owned polls (the calls below) do.
+ * Caller-owned polls take a mac_cons through the calls below; the native MADS driver (candidates
+ * generated on the device) through mac_mads_run_cons / mac_mads_begin_cons.
  *
  * mac_cons_mask: one feasibility byte (1 feasible, 0 infeasible) per candidate of the 3N x K
  * column-major matrix, one kernel launch (k_cons.h: the UAVs counting-sorted by x into cells in LDS,
@@ -223,10 +223,11 @@ int32_t mac_cons_mask_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t three
  * the objective of every candidate the constraints reject replaced by +inf — the lowest-index
  * minimiser (ties to the lowest original index), {+inf, -1} when nothing is feasible; obj_out holds
  * +inf at rejected candidates and at those failing cons3. Three steps on one stream: the mask
- * launch, the unchanged poll chain, a one-workgroup masked argmin. Rejected candidates ARE evaluated
- * by the chain and then discarded (the objective is pure, so the result is the same; leaving them out
- * of the walks would need a mask input to the chain's prep kernels). N <= 2048 when a constraint is
- * on. cons = NULL or all off: forwards to mac_poll_best_f64 (bit-identical outputs). Threading as
+ * launch, the unchanged poll chain, a one-workgroup masked argmin. On this matrix path rejected
+ * candidates ARE evaluated by the chain and then discarded (the objective is pure, so the result is
+ * the same; the matrix prep kernels take no mask, so that config 4's launches stay as they are). The
+ * native MADS driver's generated polls leave them out instead (mac_mads_run_cons). N <= 2048 when a
+ * constraint is on. cons = NULL or all off: forwards to mac_poll_best_f64 (bit-identical outputs). Threading as
  * mac_poll_best_f64. */
 int32_t mac_poll_best_cons_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
                                const double* r_max, double penalty,
@@ -261,8 +262,9 @@ typedef struct mac_mads_stats {
     double host_perm_s;    /*           next iteration's permutations (overlaps the device)    */
     double wait_s;         /*           waiting for the device                                 */
     double host_post_s;    /*           incumbent update after each poll                       */
-    int64_t feasible_evaluations; /* poll candidates that passed cons3 and were evaluated (this
-                                     stepper's shard; the start point's evaluation not counted) */
+    int64_t feasible_evaluations; /* poll candidates that passed cons3 (and the mac_cons, when one is
+                                     given) and were evaluated (this stepper's shard; the start
+                                     point's evaluation not counted) */
     int64_t rejected_polls;       /* iterations cons3 rejected whole with no evaluation: every
                                      variable's diagonal step +-2^ell alone breaks its UAV's d_lim
                                      (src/TDM_Constraints.jl:67), so no candidate passes — a
@@ -275,6 +277,18 @@ typedef struct mac_mads_stats {
 int32_t mac_mads_run(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                      double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                      const mac_mads_params* params, double* x_out, mac_mads_stats* stats);
+/* The same loop under a mac_cons (src/FullSimulation.jl:86,97: MADS gets [cons_ext, cons3]): every
+ * poll enqueues one mask launch over its generated candidates before its chain, on the poll's stream
+ * (k_cons.h cons_mask_gen_kernel: mac_cons_mask's sort and pair test, one byte per candidate), and
+ * the chain's prep launch treats a rejected candidate as a cons3 failure: objective +inf, not
+ * evaluated (left out of the walks when N <= 512; evaluated and then +inf above, as cons3 there),
+ * not counted in feasible_evaluations. f(x0) is +inf when x0 itself is rejected. cons = NULL or all
+ * constraints off: mac_mads_run itself — no mask launch, bit-identical outputs and statistics.
+ * N > 2048 with a constraint on: MAC_E_INVAL. */
+int32_t mac_mads_run_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* params, double* x_out, mac_mads_stats* stats,
+                          const mac_cons* cons);
 
 /* The same loop one iteration at a time, for the multi-GPU poll (BASELINE config 5 "8 GPUs";
  * src/TDM_STATIC_opt.jl:129, SetMaxEvals's poll-level parallelism). A stepper owns the shard
@@ -293,6 +307,12 @@ int32_t mac_mads_begin(mac_ctx* ctx, const double* x0, int64_t three_n, const do
                        double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                        const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
                        mac_mads** out);
+/* mac_mads_begin under a mac_cons (see mac_mads_run_cons): every poll of the stepper — mac_mads_poll
+ * and mac_mads_poll_ahead, any shard — is masked; the ranks of a sharded loop pass the same cons. */
+int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
+                            mac_mads** out, const mac_cons* cons);
 int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* best_idx);
 int32_t mac_mads_update(mac_mads* m, double best_obj, int64_t best_idx);
 int32_t mac_mads_result(mac_mads* m, double* x_out, mac_mads_stats* stats);
@@ -304,7 +324,8 @@ int32_t mac_mads_result(mac_mads* m, double* x_out, mac_mads_stats* stats);
  *   mac_mads_poll_ahead  evaluates (this stepper's shard of) the poll of the iteration `ahead`
  *                        failures past the current one, without advancing; done = 1 when that
  *                        poll does not exist (iteration limit or ell - ahead < 0); feasible (may be
- *                        NULL): its candidates that passed cons3 (evaluated);
+ *                        NULL): its candidates that passed cons3 and the stepper's mac_cons
+ *                        (evaluated);
  *   mac_mads_advance     applies one iteration's result (the poll at ahead = 0) as
  *                        mac_mads_update does, without a prior mac_mads_poll; moved = 1 when the
  *                        incumbent moved (success). Same iterates as the sequential loop. */
@@ -452,8 +473,9 @@ int32_t mac_profile_split(mac_ctx* ctx, double* prep_ms, double* walk_ms, double
  *   0 prep_kernel, 1 disk_index_kernel, 2 walk_setup_kernel, 3 coverage_tiled_poll_kernel,
  *   4 coverage_poll_kernel, 5 the crowded-poll shared-entry pass (shared_or_kernel on equal
  *   weights, shared_bits_kernel otherwise), 6 finalize_kernel (five-launch chain), 7 fiw_kernel and
- *   8 fin2_kernel (the fused chain) (MAC_PROF_ROLES = 9). */
-#define MAC_PROF_ROLES 9
+ *   8 fin2_kernel (the fused chain), 9 cons_mask_gen_kernel (the native MADS driver's swarm mask, one
+ *   launch per masked poll) (MAC_PROF_ROLES = 10). */
+#define MAC_PROF_ROLES 10
 int32_t mac_profile_kernels(mac_ctx* ctx, double* ms_out, int64_t* launches_out, int32_t n_roles);
 
 /* ---- fire generator (src/DynamicArea.jl, config 5) ------------------------------ */

@@ -176,7 +176,8 @@ end
 poll_best(cands, r_max; prev, d_lim, tan_half_fov, cons) — one whole MADS poll on the GPU: every
 candidate's objective, cons3 (src/TDM_Constraints.jl:54-75) as an extreme barrier (+Inf), and
 the lowest-index minimiser. With `cons::MacCons` (mac_poll_best_cons_f64) the candidates cons8 /
-cons7 reject are +Inf as well (they are still evaluated by the chain, then discarded); `nothing`
+cons7 reject are +Inf as well (on this matrix path they are still evaluated by the chain, then
+discarded; mads_run's generated polls leave them out); `nothing`
 keeps the plain call. Returns (best_obj, best_idx (1-based, 0 if none feasible), objs).
 """
 function poll_best(cands::Matrix{Float64}, r_max::Vector{Float64}, ctx::MacContext;
@@ -295,26 +296,37 @@ struct MadsStats
 end
 
 """
-mads_run(x0, r_max, ctx; prev, d_lim, tan_half_fov, n_iter, ell0, ell_max, seed) — the whole
+mads_run(x0, r_max, ctx; prev, d_lim, tan_half_fov, n_iter, ell0, ell_max, seed, cons) — the whole
 granular-MADS loop inside libmaxcover (complete LTMADS poll generated on the device, cons3 as
 extreme barrier): the batched stand-in for TDM_STATIC_opt.optimize (src/TDM_STATIC_opt.jl:118-169).
-Returns (x, stats::MadsStats).
+With `cons::MacCons` (mac_mads_run_cons) every poll also applies cons8 / cons7 on the device — the
+`cons_ext` slot of the reference's [cons_ext, cons3] — and the candidates they reject are not
+evaluated; `nothing` keeps the plain call. Returns (x, stats::MadsStats).
 """
 function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                   penalty::Float64 = 1e5, prev::Union{Nothing,Vector{Float64}} = nothing,
                   d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
                   n_iter::Integer = 100, ell0::Integer = 2, ell_max::Integer = 6,
-                  seed::Integer = 20250216)
+                  seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing)
     x = similar(x0)
     prm = Ref(MadsParams(n_iter, ell0, ell_max, UInt64(seed)))
     st = Ref{MadsStats}()
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
     GC.@preserve prev d_lim begin
-        check(ccall((:mac_mads_run, libmaxcover), Int32,
-                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
-                     Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats}),
-                    ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st))
+        if cons === nothing
+            check(ccall((:mac_mads_run, libmaxcover), Int32,
+                        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                         Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats}),
+                        ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st))
+        else
+            check(ccall((:mac_mads_run_cons, libmaxcover), Int32,
+                        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                         Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats},
+                         Ref{MacCons}),
+                        ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st,
+                        Ref(cons)))
+        end
     end
     return x, st[]
 end

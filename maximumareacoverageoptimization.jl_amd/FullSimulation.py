@@ -59,19 +59,39 @@ def cons3_ok(prev: np.ndarray, x: np.ndarray, d_lim: np.ndarray) -> bool:
     return True
 
 
+def split_cons_ext(cons_ext):
+    """The ``cons_ext`` slot of the reference's MADS call ([cons_ext, cons3], :86, :97) as the one
+    mac_cons mapping the native driver takes (TDM_Constraints.merge_mac_cons; None: nothing on).
+    ``cons1`` (always true) is dropped. A constraint the device cannot apply — a plain callable, or
+    a second constraint of a kind already merged — raises ValueError naming it: the native driver
+    generates its candidates on the device and calls no host function. Needs no GPU."""
+    from .TDM_Constraints import cons1, merge_mac_cons
+    if callable(cons_ext):
+        cons_ext = [cons_ext]
+    merged, plain = merge_mac_cons([c for c in (cons_ext or ()) if c is not cons1])
+    if plain:
+        names = ", ".join(getattr(c, "__name__", repr(c)) for c in plain)
+        raise ValueError(f"cons_ext: {names} cannot run in the native MADS driver (no mac_cons data, "
+                         "or a second constraint of a kind already given)")
+    return merged
+
+
 class Simulation:
     """The MPC loop as a stepper (one ``step()`` per timestep t = 1, 2, ...). Point source:
     ``fire`` (GPU CA: its initial points first, one CA step per MPC step), ``firepoints`` (table
     rows: rows 1..10 initially, then row t+10), or ``initial_points`` alone (static).
     ``attribution=True`` adds ``owned`` and ``exclusive`` (N doubles each, Context.area_by_disk of
-    the step's MADS output on the step's list) to every record."""
+    the step's MADS output on the step's list) to every record. ``cons_ext``: the swarm constraints
+    MADS gets beside cons3 (TDM_Constraints.create_cons8 / create_cons7; split_cons_ext), applied on
+    the device by every poll in all three modes (single, sharded, speculative)."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
                  shard=None, gather=None, speculate: bool | None = None, device=None,
-                 attribution: bool = False):
+                 attribution: bool = False, cons_ext=()):
         self.ctx = ctx
+        self.cons = split_cons_ext(cons_ext)
         # per-UAV attribution of each step's MADS output (one mac_area_by_disk_f64 call per step)
         self.attribution = bool(attribution)
         self.x_prev = np.asarray(starting_circles, dtype=np.float64).copy()
@@ -139,6 +159,8 @@ class Simulation:
                 single_input = drone_locs
         kw = dict(prev=self.x_prev, d_lim=self.d_lim, tan_half_fov=self.tan, n_iter=self.N_iter,
                   ell0=self.ell0, ell_max=self.ell_max, seed=self.seed + t)
+        if self.cons is not None:
+            kw["cons"] = self.cons
         if self.shard is None or self.shard[1] == 1:
             x_out, st = ctx.mads_run(single_input, self.r_max, 1e5, **kw)
         elif self.speculate:

@@ -46,7 +46,7 @@ MAC_STORE_F32 = 1
 PROF_ROLES = ("prep_kernel",  # (role 0: the prep launch, prep_kernel or prep_x_kernel)
               "disk_index_kernel", "walk_setup_kernel", "coverage_tiled_poll_kernel",
               "coverage_poll_kernel", "shared_or_kernel", "finalize_kernel", "fiw_kernel",
-              "fin2_kernel")
+              "fin2_kernel", "cons_mask_gen_kernel")
 
 ALGOS = {"auto": MAC_ALGO_AUTO, "scan": MAC_ALGO_SCAN, "tiled": MAC_ALGO_TILED,
          "poll": MAC_ALGO_POLL}
@@ -73,7 +73,7 @@ EXPORTS = (
     "mac_comm_unique_id", "mac_comm_init", "mac_poll_exchange", "mac_exchange_records",
     "mac_area_by_disk_f64", "mac_area_by_disk_batch_f64", "mac_area_by_disk_dev_f64",
     "mac_cons_mask_f64", "mac_cons_mask_dev_f64", "mac_poll_best_cons_f64",
-    "mac_poll_best_cons_dev_f64",
+    "mac_poll_best_cons_dev_f64", "mac_mads_run_cons", "mac_mads_begin_cons",
 )
 
 
@@ -205,6 +205,12 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_append_points_f64": ([_vp, _dp, _dp, _dp, _i64], _i32),
         "mac_mads_run": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                           ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats)], _i32),
+        "mac_mads_run_cons": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                               ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats),
+                               ctypes.POINTER(Cons)], _i32),
+        "mac_mads_begin_cons": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                                 ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
+                                 ctypes.POINTER(Cons)], _i32),
         "mac_append_points_dev_f64": ([_vp, _vp, _vp, _vp, _i64], _i32),
         "mac_fire_last_error": ([], ctypes.c_char_p),
         "mac_fire_thresholds": ([ctypes.POINTER(FireParams), _dp], None),
@@ -711,9 +717,11 @@ class Context:
     # -- native MADS driver
     def mads_run(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                  tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-                 seed: int = 20250216):
+                 seed: int = 20250216, cons=None):
         """mac_mads_run: the whole MADS loop in libmaxcover (candidates generated on the device).
-        Returns (x, stats dict)."""
+        ``cons`` (a Cons, or anything make_cons takes, e.g. TDM_Constraints.merge_mac_cons's
+        mapping): the swarm constraints every poll applies on the device (mac_mads_run_cons); None
+        keeps the plain call. Returns (x, stats dict)."""
         x = _f64(x0)
         rm = _f64(r_max)
         pv = _f64(prev) if prev is not None else None
@@ -721,19 +729,25 @@ class Context:
         out = np.empty_like(x)
         prm = MadsParams(int(n_iter), int(ell0), int(ell_max), int(seed) & (2**64 - 1))
         st = MadsStats()
-        _check(self._L.mac_mads_run(self._h, _ptr(x), x.size, _ptr(rm), float(penalty),
-                                    _ptr(pv) if pv is not None else None,
-                                    _ptr(dl) if dl is not None else None, float(tan_half_fov),
-                                    ctypes.byref(prm), _ptr(out), ctypes.byref(st)))
+        args = (self._h, _ptr(x), x.size, _ptr(rm), float(penalty),
+                _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
+                float(tan_half_fov), ctypes.byref(prm), _ptr(out), ctypes.byref(st))
+        cs = make_cons(cons)
+        if cs is None:
+            _check(self._L.mac_mads_run(*args))
+        else:
+            _check(self._L.mac_mads_run_cons(*args, ctypes.byref(cs)))
         return out, {k: getattr(st, k) for k, _ in MadsStats._fields_}
 
     def mads_stepper(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                      tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2,
-                     ell_max: int = 6, seed: int = 20250216, shard=None) -> "MadsStepper":
+                     ell_max: int = 6, seed: int = 20250216, shard=None,
+                     cons=None) -> "MadsStepper":
         """mac_mads_begin: the native loop one poll at a time over the candidate shard
-        ``shard`` = (lo, hi) of each poll's 2n candidates (None: the whole poll)."""
+        ``shard`` = (lo, hi) of each poll's 2n candidates (None: the whole poll). ``cons``: as
+        mads_run's (mac_mads_begin_cons; every rank of a sharded loop passes the same one)."""
         st = MadsStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
-                         ell_max, seed, shard)
+                         ell_max, seed, shard, cons)
         self._steppers.add(st)
         return st
 
@@ -932,7 +946,7 @@ class MadsStepper:
     shards; result() -> (x, stats). dist.mads_loop drives it."""
 
     def __init__(self, ctx: Context, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter,
-                 ell0, ell_max, seed, shard):
+                 ell0, ell_max, seed, shard, cons=None):
         self._L = ctx._L
         self._ctx = ctx   # keeps the context alive while the stepper lives
         x = _f64(x0)
@@ -944,10 +958,14 @@ class MadsStepper:
         self.shard = (lo, hi)
         prm = MadsParams(int(n_iter), int(ell0), int(ell_max), int(seed) & (2**64 - 1))
         h = _vp()
-        _check(self._L.mac_mads_begin(ctx._h, _ptr(x), x.size, _ptr(rm), float(penalty),
-                                      _ptr(pv) if pv is not None else None,
-                                      _ptr(dl) if dl is not None else None, float(tan_half_fov),
-                                      ctypes.byref(prm), lo, hi, ctypes.byref(h)))
+        args = (ctx._h, _ptr(x), x.size, _ptr(rm), float(penalty),
+                _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
+                float(tan_half_fov), ctypes.byref(prm), lo, hi, ctypes.byref(h))
+        cs = make_cons(cons)
+        if cs is None:
+            _check(self._L.mac_mads_begin(*args))
+        else:
+            _check(self._L.mac_mads_begin_cons(*args, ctypes.byref(cs)))
         self._h = h
         self._done, self._bo, self._bi = _i32(), ctypes.c_double(), _i64()
 
@@ -962,7 +980,7 @@ class MadsStepper:
     def poll_ahead(self, ahead: int):
         """mac_mads_poll_ahead: (done, best_obj, best_idx, feasible) of the poll that follows
         `ahead` failures of the current iteration, the stepper unchanged; feasible = its
-        candidates that passed cons3."""
+        candidates that passed cons3 (and the stepper's swarm constraints)."""
         fe = _i64()
         _check(self._L.mac_mads_poll_ahead(self._h, int(ahead), ctypes.byref(self._done),
                                            ctypes.byref(self._bo), ctypes.byref(self._bi),

@@ -44,6 +44,7 @@
 #include "predicate.h"
 #include "k_common.h"
 #include "k_final.h"
+#include "k_prep.h"
 
 #pragma clang fp contract(off)
 
@@ -84,12 +85,13 @@ static inline ConsArgs cons_args(double d_sep, double zone_y, double zone_r)
     return a;
 }
 
-// Workgroup = candidate (column k of the 3N x K matrix). Thread t loads elements s * 256 + t (s < S,
-// 256 S >= N) and owns cell t of the kConsCells cells. Dynamic LDS: 17 * 256 S bytes (x, y and the
-// cell of every sorted position).
-template <int S>
-__global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __restrict__ cands, int N,
-                                                             ConsArgs a, uint8_t* __restrict__ feasible)
+// The sort-and-sweep of one candidate by one workgroup, shared by the matrix and the generated-poll
+// kernels: load(e, x, y, r) gives UAV e's values (r is read only under cons7). Thread t loads
+// elements s * 256 + t (s < S, 256 S >= N) and owns cell t of the kConsCells cells. Dynamic LDS:
+// 17 * 256 S bytes (x, y and the cell of every sorted position). Returns (thread 0's value is the
+// candidate's) whether a constraint rejects the candidate.
+template <int S, class Load>
+__device__ __forceinline__ bool cons_violates(Load load, int N, const ConsArgs& a)
 {
     static_assert(kConsCells == kConsBlock, "one cell per thread");
     constexpr int P = kConsBlock * S;
@@ -104,7 +106,6 @@ __global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __r
     __shared__ int wsum[kConsBlock / kWave];
     __shared__ int viol;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const double* __restrict__ c = cands + (size_t)blockIdx.x * (size_t)(3 * N);
     const double inf = __builtin_inf();
     if (tid == 0) viol = 0;
     cnt[tid] = 0;
@@ -117,7 +118,8 @@ __global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __r
         kx[s] = inf;   // +inf: not a UAV of the pair tests (past N, or a non-finite coordinate)
         ky[s] = 0.0;
         if (e < N) {
-            const double x = c[e], y = c[N + e], r = c[2 * N + e];
+            double x, y, r;
+            load(e, x, y, r);
             bad |= a.zone && y < a.zone_y && r > a.zone_r;
             if (__builtin_fabs(x) < inf && __builtin_fabs(y) < inf) {
                 kx[s] = x;
@@ -226,7 +228,47 @@ __global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __r
         }
         __syncthreads();
     }
-    if (tid == 0) feasible[blockIdx.x] = viol ? 0 : 1;
+    return viol != 0;
+}
+
+// Workgroup = candidate (column k of the 3N x K matrix).
+template <int S>
+__global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __restrict__ cands, int N,
+                                                             ConsArgs a, uint8_t* __restrict__ feasible)
+{
+    const double* __restrict__ c = cands + (size_t)blockIdx.x * (size_t)(3 * N);
+    const bool v = cons_violates<S>(
+        [&](int e, double& x, double& y, double& r) {
+            x = c[e];
+            y = c[N + e];
+            r = c[2 * N + e];
+        },
+        N, a);
+    if (threadIdx.x == 0) feasible[blockIdx.x] = v ? 0 : 1;
+}
+
+// The mask over a generated poll (the native MADS driver, k_prep.h CandSrc): workgroup = candidate k
+// of the source (a rank's shard: candidate src.k0 + k of the poll), its x and y drawn through
+// src.get, r only under cons7. One byte per candidate of the shard, read by the poll's prep launch
+// (PrepArgs.mask8). In the pipelined loop the step comes from the device state, and once the loop
+// has stopped the launch returns without writing (uniform per workgroup, before any barrier).
+template <int S>
+__global__ __launch_bounds__(kConsBlock) void cons_mask_gen_kernel(uint64_t* ts, CandSrc src, int N, ConsArgs a,
+                                                                 uint8_t* __restrict__ feasible)
+{
+    ts_begin(ts);   // profiling only (k_common.h)
+    if (src.resolve(true)) {
+        const int k = (int)blockIdx.x;
+        const bool v = cons_violates<S>(
+            [&](int e, double& x, double& y, double& r) {
+                x = src.get(k, e, N);
+                y = src.get(k, N + e, N);
+                r = a.zone ? src.get(k, 2 * N + e, N) : 0.0;
+            },
+            N, a);
+        if (threadIdx.x == 0) feasible[k] = v ? 0 : 1;
+    }
+    ts_end(ts);
 }
 
 // The masked poll's last launch, one workgroup: obj[k] <- +inf where feasible[k] == 0 (in place),

@@ -226,6 +226,7 @@ struct PrepArgs {
                                // each B entry for both: prep_cand)
     int nchain;                // workgroups
     int skip_failed;           // 1: the records leave out cons3 failures (no area is reported for them)
+    int xbase;                 // (prep_x_kernel) workgroup cw also takes candidate xbase + cw when < K
     int4* prec;                // [nchain][N] records (null: no poll walk)
     Grid g;
     uint32_t* keysP;           // packed keys (null: none), one row per disk, pitch ldk
@@ -243,8 +244,29 @@ struct PrepArgs {
     MadsState* mst_w;
     unsigned long long* feas;  // += the candidates that pass cons3 (null: not counted)
     int* lreset;               // the fused chain's hand-off list count, zeroed for this poll (null: none)
-    int xbase;                 // (prep_x_kernel) workgroup cw also takes candidate xbase + cw when < K
+    // generated polls under swarm constraints (k_cons.h cons_mask_gen_kernel; null: none): one byte
+    // per candidate of the source, 0 = rejected. A rejected candidate counts as a cons3 failure
+    // (vp = +inf, not in feas; with skip_failed and N <= kPrepU in dead8 and out of the records,
+    // the displacement bound and the key flag). Matrix sources do not read it. (xbase sits in
+    // the padding above, so the kernel arguments keep their size.)
+    const uint8_t* mask8;
 };
+
+// The candidates of a workgroup's slots the swarm mask rejects, as a bit per slot (uniform: scalar
+// loads). cand(c) >= K: absent.
+template <int NC, class Cand>
+__device__ __forceinline__ uint32_t prep_masked(const uint8_t* mask8, int K, Cand cand)
+{
+    uint32_t m = 0u;
+    if (mask8) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const int k = cand(c);
+            if (k < K && mask8[k] == 0) m |= 1u << c;
+        }
+    }
+    return m;
+}
 
 // The fused chain's prep over a matrix source (prep_x_kernel): kPrepCX candidates per workgroup
 // and floor(K / kPrepCX) workgroups, the remainder (fewer than the workgroups) one more each to
@@ -369,7 +391,11 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
     // cover. With one block of UAVs (N <= kPrepU) their failure is known before the records are
     // written, so the records leave them out (the regions, and with them the walks' work, shrink
     // to the feasible candidates; the index maps them to an inert position, k_index.h). Uniform.
-    const bool excl = obj && pa.prev && (a.prec || a.pd) && a.skip_failed && N <= kPrepU;
+    // (a generated poll's swarm mask joins the failures: mdead, bit c = slot c rejected)
+    uint32_t mdead = 0u;
+    if constexpr (!kMat) mdead = prep_masked<NC>(obj ? a.mask8 : nullptr, K, cand);
+    const bool masked = !kMat && a.mask8 != nullptr;
+    const bool excl = obj && (pa.prev || masked) && (a.prec || a.pd) && a.skip_failed && N <= kPrepU;
     double dmx = -__builtin_inf(), dmy = -__builtin_inf(), dmr = -__builtin_inf();   // (pd)
     double dml = -__builtin_inf();   // (pd) max r0 - r
     uint32_t dead = 0u;   // (excl) bit c: candidate c fails cons3 (0 otherwise)
@@ -448,7 +474,7 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
             MAC_PREP_STAMP(1 + 3 * (ib / kPrepU));
             lds_barrier();   // every wave's terms and failures
             if (excl) {   // (the records below leave the failures out)
-                dead = 0u;
+                dead = mdead;
 #pragma unroll
                 for (int w = 0; w < kPrepU / kWave; ++w) dead |= wbadm[w];
                 if (a.mst_w) {
@@ -465,6 +491,7 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
                 // share of them after the fold, which sets the launch's length)
 #pragma unroll
                 for (int w = 0; w < kPrepU / kWave; ++w) bad |= wbad[w][u] != 0;
+                if constexpr (!kMat) bad |= ((mdead >> u) & 1u) != 0;
                 if (!bad) {   // (a cons3 failure's vp is +inf: no chain to fold)
                     // the chain's wave first at issue: the dependent adds are the launch's
                     // critical path, the other waves on its SIMD have slack
@@ -660,7 +687,11 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     };
     const bool obj = a.vp != nullptr;
     const PenArgs& pa = a.pa;
-    const bool excl = obj && pa.prev && a.skip_failed;
+    // (a generated poll's swarm mask joins the failures: mdead, bit c = slot c rejected)
+    uint32_t mdead = 0u;
+    if constexpr (kGen) mdead = prep_masked<NC>(obj ? a.mask8 : nullptr, K, cand);
+    const bool masked = kGen && a.mask8 != nullptr;
+    const bool excl = obj && (pa.prev || masked) && a.skip_failed;
     const bool iv = !fw && u < N;
     const int ii = min(u, N - 1);
     MAC_PREP_STAMP(0);
@@ -732,6 +763,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     if (obj) {
         lds_barrier();   // every wave's terms and failures
         if (excl) {
+            dead = mdead;
 #pragma unroll
             for (int w = 0; w < NW; ++w) dead |= wbadm[w];
             if (a.mst_w) {
@@ -750,6 +782,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
         if (obj && lane < NC) {
 #pragma unroll
             for (int w = 0; w < NW; ++w) bad |= wbad[w][lane] != 0;
+            if constexpr (kGen) bad |= ((mdead >> lane) & 1u) != 0;
             if (!bad) {   // (a cons3 failure's vp is +inf: no chain to fold)
                 // batches of 2 kB terms (pair reads), the next batch's reads in flight while this
                 // batch's adds run; ping-pong buffers, the reads past the last batch re-read it

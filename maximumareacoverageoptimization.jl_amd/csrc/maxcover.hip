@@ -274,7 +274,7 @@ struct mac_ctx {
     struct Prof { int64_t a, na, b, nb; int64_t K; const int* mode; int algo;
                   int64_t c = -1, nc = 0, f = -1, nf = 0;
                   int64_t role[MAC_PROF_ROLES][2] = {{-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0},
-                                                     {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}}; };
+                                                     {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}}; };
     std::vector<Prof> prof;                          // recorded launches (guarded by mu)
     DevBuf stamps;
     int64_t stamp_cap = 0, stamp_used = 0;           // in workgroup slots (guarded by mu)
@@ -641,7 +641,8 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                          const double* d_prev, const double* d_dlimT, const double* d_dlim_raw,
                          double tan_half_fov, double* d_area, double* d_obj, double* d_best,
                          int64_t idx_base, uint64_t* d_mirror = nullptr, uint64_t mirror_seq = 0,
-                         const FinBest* fb_mads = nullptr, unsigned long long* d_feas = nullptr)
+                         const FinBest* fb_mads = nullptr, unsigned long long* d_feas = nullptr,
+                         const ConsArgs* gcons = nullptr)
 {
     const int64_t M = ctx->M;
     int n_poll = N, n_other = 1;
@@ -651,6 +652,7 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
     int64_t ts_a = -1, ts_na = 0, ts_b = -1, ts_nb = 0, ts_c = -1, ts_nc = 0, ts_f = -1, ts_nf = 0;
     int64_t ts_i = -1, ts_ni = 0, ts_s = -1, ts_ns = 0, ts_g = -1, ts_ng = 0;   // index, set-up, bits
     int64_t ts_w = -1, ts_nw = 0;                                               // the fused kernel
+    int64_t ts_m = -1, ts_nm = 0;                                               // the swarm mask
     auto take_ts = [&](int64_t nwg, int64_t& base, int64_t& n) -> uint64_t* {
         if (!ctx->profile) return nullptr;
         std::lock_guard<std::mutex> lk(ctx->mu);
@@ -688,19 +690,37 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                         ts_w >= 0 ? MAC_ALGO_POLL : tiled ? MAC_ALGO_TILED : MAC_ALGO_SCAN, ts_c, ts_nc,
                         ts_f, ts_nf};
         if (ts_c >= 0) {   // a poll chain: every launch's stamps by role (mac_profile_kernels)
-            const int64_t r[MAC_PROF_ROLES][2] = {{ts_c, ts_nc}, {ts_i, ts_ni}, {ts_s, ts_ns},
+            const int64_t r[MAC_PROF_ROLES - 1][2] = {{ts_c, ts_nc}, {ts_i, ts_ni}, {ts_s, ts_ns},
                                                   {ts_w >= 0 ? -1 : ts_a, ts_w >= 0 ? 0 : ts_na},
                                                   {ts_b, ts_nb}, {ts_g, ts_ng},
                                                   {ts_w >= 0 ? -1 : ts_f, ts_w >= 0 ? 0 : ts_nf},
                                                   {ts_w, ts_nw},
                                                   {ts_w >= 0 ? ts_f : -1, ts_w >= 0 ? ts_nf : 0}};
-            for (int q = 0; q < MAC_PROF_ROLES; ++q) {
+            for (int q = 0; q < MAC_PROF_ROLES - 1; ++q) {
                 p.role[q][0] = r[q][0];
                 p.role[q][1] = r[q][1];
             }
         }
+        p.role[MAC_PROF_ROLES - 1][0] = ts_m;   // (with or without a poll chain)
+        p.role[MAC_PROF_ROLES - 1][1] = ts_nm;
         ctx->prof.push_back(p);
     };
+
+    // a generated poll under swarm constraints (the native MADS driver): the mask launch first, one
+    // byte per candidate into the lane's buffer (reused stream-ordered), read by the prep launch
+    const uint8_t* d_mask8 = nullptr;
+    if (gcons && !src.cands && d_obj && K > 0) {
+        L->cmask.reserve((size_t)K);
+        d_mask8 = L->cmask.as<uint8_t>();
+        const int S = cons_slots(N);   // UAVs per thread: 1, 2, 4, 8 (N <= kConsMaxN, checked at begin)
+        void (*const kern)(uint64_t*, CandSrc, int, ConsArgs, uint8_t*) =
+            S == 1 ? cons_mask_gen_kernel<1> : S == 2 ? cons_mask_gen_kernel<2>
+          : S == 4 ? cons_mask_gen_kernel<4> : cons_mask_gen_kernel<8>;
+        uint64_t* tsm = take_ts(K, ts_m, ts_nm);
+        hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock), (uint32_t)(17 * kConsBlock * S), s, tsm,
+                           src, N, *gcons, L->cmask.as<uint8_t>());
+        HCK(hipGetLastError());
+    }
 
     CandSrc isrc = src;
     const int target = 8 * ctx->cus;
@@ -758,7 +778,7 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             L->frows.reserve((counts ? sizeof(unsigned) : sizeof(double)) * (size_t)N * ldk);
             if (L->fwhint.grow(sizeof(int) * kFwHints)) HCK(hipMemsetAsync(L->fwhint.p, 0, L->fwhint.cap, s));
             // cons3 failures are left out of the walk when only objectives are asked for
-            const bool excl = d_obj && d_prev && !d_area && N <= kPrepU;
+            const bool excl = d_obj && (d_prev || d_mask8) && !d_area && N <= kPrepU;
             if (excl) L->dead8.reserve((size_t)ldk + 16);   // (the fused kernel reads 4-B words)
             L->fwlist.reserve(sizeof(int4) * (size_t)std::max(N, kF2Pre));
             if (L->fwcount.grow(sizeof(int))) HCK(hipMemsetAsync(L->fwcount.p, 0, L->fwcount.cap, s));
@@ -781,8 +801,9 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             pr.ldk = ldk;
             pr.pd = L->pd.as<double4>();
             pr.dead8 = excl ? L->dead8.as<uint8_t>() : nullptr;
-            pr.mst_w = excl && fb_mads ? fb_mads->st : nullptr;
+            pr.mst_w = excl && d_prev && fb_mads ? fb_mads->st : nullptr;
             pr.feas = d_feas;
+            pr.mask8 = d_mask8;
             pr.lreset = L->fwcount.as<int>();
             uint64_t* tsk = take_ts(nprep, ts_c, ts_nc);
             using hclk = std::chrono::steady_clock;
@@ -887,6 +908,7 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
         pr.pair = pair ? 1 : 0;
         pr.g = ctx->grid;
         pr.feas = d_feas;
+        pr.mask8 = d_mask8;
         // the pipelined MADS loop: a poll cons3 rejects whole is decided by the prep (k_prep.h
         // MadsState.skip) when its failures are left out of the walk (the prep's excl)
         pr.mst_w = fb_mads && poll_possible && d_obj && d_prev && !d_area && N <= kPrepU ? fb_mads->st
@@ -2201,6 +2223,8 @@ struct mac_mads {
     double penalty = 1e5, tan_half_fov = 1.0;
     const double* d_prev = nullptr;
     const double* d_dlimT = nullptr;
+    ConsArgs cons{};              // the swarm constraints (mac_mads_begin_cons): every poll's mask launch
+    bool has_cons = false;
     std::vector<double> x;
     double f = INFINITY;
     int64_t evals = 0, it = 0, rejected = 0, succ = 0;
@@ -2320,7 +2344,7 @@ static void mads_best_of(mac_mads* m, const CandSrc& src, int Kc, int64_t idx_ba
                  m->d_prev ? m->L->dlimraw.as<double>() : nullptr, m->tan_half_fov,
                  nullptr, m->L->obj.as<double>(), mads_best_ptr(m), idx_base,
                  slot ? m->d_slot : nullptr, slot ? ++m->seq : 0, nullptr,
-                 slot ? m->d_feas.as<unsigned long long>() : nullptr);
+                 slot ? m->d_feas.as<unsigned long long>() : nullptr, m->has_cons ? &m->cons : nullptr);
     if (!slot) HCK(hipMemcpyAsync(m->hb, mads_best_ptr(m), 16, hipMemcpyDeviceToHost, m->s));
 }
 
@@ -2364,6 +2388,15 @@ int32_t mac_mads_begin(mac_ctx* ctx, const double* x0, int64_t three_n, const do
                        const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
                        mac_mads** out)
 {
+    return mac_mads_begin_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
+                               shard_hi, out, nullptr);
+}
+
+int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
+                            mac_mads** out, const mac_cons* cons)
+{
     ABI_BEGIN
     if (!out) return fail(MAC_E_INVAL, "null out");
     *out = nullptr;
@@ -2378,8 +2411,15 @@ int32_t mac_mads_begin(mac_ctx* ctx, const double* x0, int64_t three_n, const do
     const int n = (int)three_n, K = 2 * n;
     if (shard_lo < 0 || shard_hi > K || shard_lo > shard_hi)
         return fail(MAC_E_INVAL, "shard outside [0, 2n)");
+    ConsArgs ca{};
+    const bool has_cons = cons_active(cons, &ca);
+    if (has_cons && N > kConsMaxN)
+        return fail(MAC_E_INVAL, "mac_mads_begin_cons: N = " + std::to_string(N) + " > " +
+                                     std::to_string(kConsMaxN) + " UAVs under a swarm constraint");
     set_device(ctx);
     mac_mads* m = new mac_mads();
+    m->cons = ca;
+    m->has_cons = has_cons;
     m->t0 = std::chrono::steady_clock::now();
     m->ctx = ctx;
     try {
@@ -2429,8 +2469,17 @@ int32_t mac_mads_begin(mac_ctx* ctx, const double* x0, int64_t three_n, const do
         std::copy(m->x.begin(), m->x.end(), m->hx);
         HCK(hipMemcpyAsync(L->cands.p, m->hx, sizeof(double) * three_n, hipMemcpyHostToDevice, s));
         mads_best_of(m, matrix_src(L->cands.as<double>(), N), 1, 0);
+        if (has_cons) {   // ... or a swarm constraint: its byte from the matrix mask
+            L->cmask.reserve(1);
+            cons_mask_enqueue(s, L->cands.as<double>(), N, 1, ca, L->cmask.as<uint8_t>());
+        }
         HCK(hipStreamSynchronize(s));
         m->f = __builtin_bit_cast(int64_t, m->hb[1]) >= 0 ? m->hb[0] : INFINITY;
+        if (has_cons) {
+            uint8_t ok = 1;
+            HCK(hipMemcpy(&ok, L->cmask.p, 1, hipMemcpyDeviceToHost));
+            if (!ok) m->f = INFINITY;
+        }
         m->evals = 1;
         m->ell = prm->ell0;
         // the run's chain, from its first poll: x0 at mesh step 2^ell0 (the incumbent moves by a few
@@ -2809,7 +2858,8 @@ static void mads_run_pipelined(mac_mads* m)
         enqueue_eval(m->ctx, m->L, s, src, m->N, m->K, true, m->L->rmax.as<double>(), m->penalty,
                      m->d_prev, m->d_dlimT, m->d_prev ? m->L->dlimraw.as<double>() : nullptr,
                      m->tan_half_fov, nullptr, m->L->obj.as<double>(),
-                     m->L->best.as<double>(), 0, m->d_slot, (uint64_t)t, &fbm, &dst->feas);
+                     m->L->best.as<double>(), 0, m->d_slot, (uint64_t)t, &fbm, &dst->feas,
+                     m->has_cons ? &m->cons : nullptr);
         const auto t3 = clk::now();
         if (computed < n_iter) {   // one iteration's permutations per poll, uploaded per chunk
             perms_of(++computed);
@@ -2843,11 +2893,19 @@ int32_t mac_mads_run(mac_ctx* ctx, const double* x0, int64_t three_n, const doub
                      double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                      const mac_mads_params* prm, double* x_out, mac_mads_stats* st)
 {
+    return mac_mads_run_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
+                             nullptr);
+}
+
+int32_t mac_mads_run_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons)
+{
     ABI_BEGIN
     if (!x_out) return fail(MAC_E_INVAL, "null argument");
     mac_mads* m = nullptr;
-    int32_t rc = mac_mads_begin(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
-                                0, 2 * three_n, &m);
+    int32_t rc = mac_mads_begin_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
+                                     0, 2 * three_n, &m, cons);
     if (rc) return rc;
     if (mads_pipelinable(m)) {
         try {
