@@ -131,6 +131,53 @@ int32_t mac_append_points_f64(mac_ctx* ctx, const double* x, const double* y, co
 int32_t mac_append_points_dev_f64(mac_ctx* ctx, const double* d_x, const double* d_y,
                                   const double* d_w, int64_t m);
 
+/* ---- high-interest regions (src/FullSimulation.jl:751-754) ------------------------ */
+/* Axis-aligned boxes the reference's dynamic mode steers the swarm toward. It uses them for the
+ * r_max rule (:64-76, host side), for the importance override as a fire point is pushed
+ * (src/CellFunctions.jl:42-45 and :68-72) and for the one outcome it prints, "Percentage of Area
+ * Covered" (:537-557). The last two run on the device list here (csrc/k_regions.h).
+ * Boxes b < n_boxes: (x_lb[b], x_ub[b]) x (y_lb[b], y_ub[b]); membership is the reference's
+ *     x < x_ub && x > x_lb && y < y_ub && y > y_lb     (all strict, fp64; NaN anywhere: false),
+ * so a box with lb >= ub or a NaN bound holds nothing and an entry with a non-finite coordinate is in
+ * no box. w_high: the weight (column 4) given to every INCOMING entry strictly inside any box, the
+ * reference's (h_max*tan(FOV/2))^2*pi; NaN: weights are left alone (counting only).
+ * n_boxes = 0 (pointers may be NULL): regions off — nothing is launched and every call behaves as
+ * if regions did not exist. n_boxes < 0 or > MAC_REGIONS_MAX, or a NULL bound array with
+ * n_boxes > 0: MAC_E_INVAL, nothing changed. The call zeroes the ingest counters and touches no
+ * weight already in the list.
+ * Ingest: while regions are on, the entries arriving through mac_set_points_f64 / _f32 /
+ * _records_f64 / _dev_f64 / _dev_f32, mac_append_points_f64 / _dev_f64 and mac_fire_step(append_to)
+ * are tested once, in one launch over the incoming range only, after their copy (and widening) into
+ * the list and before it is indexed. Entries already in the list are never re-weighted (the reference
+ * overrides at push!). mac_set_points_* sets the counters to the new list's counts, an append adds to
+ * them, mac_remove_covered_f64 leaves them alone: the union counter is the reference's `total` over
+ * every point ever pushed (:539-546).
+ * Threading: as mac_set_points_* and mac_covered_flags_f64 — these calls must not overlap an
+ * evaluation or a list change. */
+#define MAC_REGIONS_MAX 64
+int32_t mac_set_regions(mac_ctx* ctx, const double* x_lb, const double* x_ub, const double* y_lb,
+                        const double* y_ub, int32_t n_boxes, double w_high);
+/* Cumulative counts of the entries that arrived inside the boxes since the counters were last reset:
+ * box_count (n_boxes values, nullable) per box, any_count (nullable) for the union, each entry once.
+ * Regions off: MAC_E_INVAL. No list is needed (the counters are then zero). */
+int32_t mac_regions_ingested(mac_ctx* ctx, int64_t* box_count, int64_t* any_count);
+/* The CURRENT list: per box (box_count / box_weight, n_boxes values each) and for the union of the
+ * boxes (any_*; an entry counts once, for the lowest-index box holding it) the number of entries
+ * and their summed weight; with circles ([x;y;r], three_n doubles; NULL with three_n = 0: none)
+ * also the union's entries covered by at least one disk (covered_*; the coverage predicate of
+ * mac_area_f64; a disk with r <= 0 or NaN covers nothing; zero without circles). The union's
+ * uncovered count after mac_remove_covered_f64 is the reference's `uncovered` (:548-554).
+ * Counts are exact. Weight sums are fp64 sums in a fixed order (per-item partials added by a second
+ * small launch: the same bits on every run of the same list, options and boxes); when every partial
+ * sum is exact they equal the list-order sum bit for bit, otherwise they agree with it to rounding
+ * (rtol 1e-12). The kernel reads only the tile rows and columns a box spans, not all M entries.
+ * Every output pointer is nullable. Errors (nothing is written): null context, regions off,
+ * N > 2048: MAC_E_INVAL; three_n % 3 != 0: MAC_E_SIZE; no list set: MAC_E_NOPOINTS. M = 0: zeros. */
+int32_t mac_region_stats_f64(mac_ctx* ctx, const double* circles, int64_t three_n,
+                             int64_t* box_count, double* box_weight,
+                             int64_t* any_count, double* any_weight,
+                             int64_t* covered_count, double* covered_weight);
+
 /* ---- objective ------------------------------------------------------------------ */
 /* calculateArea(circles, points): one candidate. */
 int32_t mac_area_f64(mac_ctx* ctx, const double* circles, int64_t three_n, double* area_out);

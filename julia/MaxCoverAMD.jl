@@ -10,14 +10,16 @@ Gabisanth/MaximumAreaCoverageOptimization.jl. Drop-in replacements for the hot p
 Plain `ccall` over the C ABI: no Julia package dependencies. The library path comes from
 ENV["MAXCOVER_LIB"] or defaults to the in-tree build. Not executed in this repository's CI
 (Julia is not installed in the build image) — the swarm-constraint wrappers (MacCons, cons_mask,
-poll_best's `cons`) included; the ctypes mirror
+poll_best's `cons`) and the high-interest region wrappers (set_regions!, regions_ingested,
+region_stats, percentage_covered) included; the ctypes mirror
 (maximumareacoverageoptimization.jl_amd/_lib.py) makes the same calls with the same arrays and
 is what the parity tests exercise. See INTEGRATION.md.
 =#
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MacCons, cons_mask
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MacCons, cons_mask,
+       set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
     joinpath(@__DIR__, "..", "maximumareacoverageoptimization.jl_amd", "libmaxcover.so"))
@@ -106,6 +108,63 @@ function area_by_disk(circles::Vector{Float64}, ctx::MacContext)
                 (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
                 ctx, circles, length(circles), owned, exclusive, area))
     return owned, exclusive, area[]
+end
+
+"""
+High-interest boxes (src/FullSimulation.jl:751-754) on the device list (mac_set_regions). While they
+are set, every fire point that arrives in the list (set_points!, the appends, the fire stream)
+strictly inside any box — `p[1] .< x_UB .&& p[1] .> x_LB .&& p[2] .< y_UB .&& p[2] .> y_LB`,
+src/CellFunctions.jl:42 — gets importance `w_high` (the reference's `(h_max*tan(FOV/2))^2*pi`, :44;
+NaN: importances left alone) and is counted. Call it before `set_points!`. At most 64 boxes.
+"""
+function set_regions!(ctx::MacContext, x_LB::Vector{Float64}, x_UB::Vector{Float64},
+                      y_LB::Vector{Float64}, y_UB::Vector{Float64}; w_high::Float64 = NaN)
+    n = length(x_LB)
+    (length(x_UB) == n && length(y_LB) == n && length(y_UB) == n) ||
+        throw(DimensionMismatch("x_LB, x_UB, y_LB, y_UB must have equal lengths"))
+    check(ccall((:mac_set_regions, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Float64),
+                ctx, x_LB, x_UB, y_LB, y_UB, n, w_high))
+    return ctx
+end
+
+clear_regions!(ctx::MacContext) = (check(ccall((:mac_set_regions, libmaxcover), Int32,
+    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Float64),
+    ctx, C_NULL, C_NULL, C_NULL, C_NULL, 0, NaN)); ctx)
+
+"""`(per_box, total)`: the points pushed inside each of the `n_boxes` boxes and inside any of them
+(each once) since the list was last set — `total_high_interest_fire_points`, src/FullSimulation.jl:537-546."""
+function regions_ingested(ctx::MacContext, n_boxes::Integer)
+    per_box = zeros(Int64, max(n_boxes, 1))
+    total = Ref{Int64}(0)
+    check(ccall((:mac_regions_ingested, libmaxcover), Int32, (Ptr{Cvoid}, Ptr{Int64}, Ref{Int64}),
+                ctx, per_box, total))
+    return per_box[1:n_boxes], total[]
+end
+
+"""
+The current list against the boxes (mac_region_stats_f64): per box and for their union (each entry
+once) the entry count and summed importance; with `circles` also the union's entries covered by at
+least one disk. After `rmvCoveredPOI!`, `any_count` is `uncovered_high_interest_fire_points` (:548-554).
+"""
+function region_stats(ctx::MacContext, n_boxes::Integer; circles::Vector{Float64} = Float64[])
+    bc = zeros(Int64, max(n_boxes, 1))
+    bw = zeros(Float64, max(n_boxes, 1))
+    ac, cc = Ref{Int64}(0), Ref{Int64}(0)
+    aw, cw = Ref{Float64}(0.0), Ref{Float64}(0.0)
+    check(ccall((:mac_region_stats_f64, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ref{Int64}, Ref{Float64},
+                 Ref{Int64}, Ref{Float64}),
+                ctx, isempty(circles) ? C_NULL : pointer(circles), length(circles), bc, bw, ac, aw, cc, cw))
+    return (box_count = bc[1:n_boxes], box_weight = bw[1:n_boxes], any_count = ac[], any_weight = aw[],
+            covered_count = cc[], covered_weight = cw[])
+end
+
+"""src/FullSimulation.jl:557, "Percentage of Area Covered" (0/0 gives NaN, as there)."""
+function percentage_covered(ctx::MacContext, n_boxes::Integer)
+    total = regions_ingested(ctx, n_boxes)[2]
+    uncovered = region_stats(ctx, n_boxes).any_count
+    return 100 - (uncovered / total) * 100
 end
 
 """K candidates as the columns of a 3N x K matrix."""

@@ -11,6 +11,7 @@ import math
 
 import numpy as np
 
+from ._lib import high_interest_mask
 from .AreaCoverageCalculation import DevicePointList, createPOI
 
 
@@ -26,10 +27,7 @@ class Cells:
 
 
 def _high_interest(new_point, box, h_max, FOV):
-    x_LB, x_UB, y_LB, y_UB = box
-    check = [(new_point[0] < xu) and (new_point[0] > xl) and (new_point[1] < yu) and
-             (new_point[1] > yl) for xl, xu, yl, yu in zip(x_LB, x_UB, y_LB, y_UB)]
-    if any(check):                                       # :42-45 / :68-72
+    if high_interest_mask(new_point[0], new_point[1], box):   # :42-45 / :68-72
         new_point[3] = (h_max * math.tan(FOV / 2)) ** 2 * math.pi
     return new_point
 

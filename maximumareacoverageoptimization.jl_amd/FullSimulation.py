@@ -26,7 +26,7 @@ import time
 
 import numpy as np
 
-from ._lib import Context
+from ._lib import Context, percentage_covered
 from .DynamicArea import DynamicArea
 
 FOV = 100 / 180 * math.pi          # :735
@@ -35,15 +35,18 @@ N_iter = 100                       # :741
 x_LB, x_UB, y_LB, y_UB = [2500], [3500], [1000], [2000]   # :751-754
 
 
-def r_max_update(drone_locs: np.ndarray, r_max: np.ndarray, N: int) -> None:
+def r_max_update(drone_locs: np.ndarray, r_max: np.ndarray, N: int, boxes=None) -> None:
     """:64-76 (t != 1): a UAV flying at ~15 m that is within h_max*tan(FOV/2) of the
-    high-interest box keeps r_max = 15*tan(FOV/2); otherwise r_max = h_max*tan(FOV/2)."""
+    high-interest box keeps r_max = 15*tan(FOV/2); otherwise r_max = h_max*tan(FOV/2).
+    ``boxes``: (x_LB, x_UB, y_LB, y_UB); None: the module's (:751-754)."""
     t2 = math.tan(FOV / 2)
+    if boxes is None:
+        boxes = (x_LB, x_UB, y_LB, y_UB)
     for i in range(N):
         if abs(15 - drone_locs[i + 2 * N] / t2) < 1:
             check = [(drone_locs[i] < xu + h_max * t2) and (drone_locs[i] > xl - h_max * t2) and
                      (drone_locs[i + N] < yu + h_max * t2) and (drone_locs[i + N] > yl - h_max * t2)
-                     for xl, xu, yl, yu in zip(x_LB, x_UB, y_LB, y_UB)]
+                     for xl, xu, yl, yu in zip(*boxes)]
             r_max[i] = 15 * t2 if any(check) else h_max * t2
 
 
@@ -83,14 +86,24 @@ class Simulation:
     ``attribution=True`` adds ``owned`` and ``exclusive`` (N doubles each, Context.area_by_disk of
     the step's MADS output on the step's list) to every record. ``cons_ext``: the swarm constraints
     MADS gets beside cons3 (TDM_Constraints.create_cons8 / create_cons7; split_cons_ext), applied on
-    the device by every poll in all three modes (single, sharded, speculative)."""
+    the device by every poll in all three modes (single, sharded, speculative).
+    ``high_interest``: the high-interest boxes ``(x_LB, x_UB, y_LB, y_UB)`` (``True``: the module's,
+    :751-754), set on the context before the first list upload (Context.set_regions) and left set
+    afterwards: every fire point pushed strictly inside one gets the weight ``w_high`` (default
+    (h_max*tan(FOV/2))^2*pi, src/CellFunctions.jl:44) on the device, the r_max rule reads the same
+    boxes, and each record gains ``hi_total`` (points ever pushed inside the boxes), ``hi_uncovered``
+    (those left in the list after the step's removal) and ``hi_percentage`` (:537-557). Every rank of
+    a multi-GPU run sets the same regions; nothing is exchanged. None: no region call is made."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
                  shard=None, gather=None, speculate: bool | None = None, device=None,
-                 attribution: bool = False, cons_ext=()):
+                 attribution: bool = False, cons_ext=(), high_interest=None, w_high=None):
         self.ctx = ctx
+        self.high_interest = self._boxes(high_interest)
+        if self.high_interest is None and w_high is not None:
+            raise ValueError("w_high needs high_interest")
         self.cons = split_cons_ext(cons_ext)
         # per-UAV attribution of each step's MADS output (one mac_area_by_disk_f64 call per step)
         self.attribution = bool(attribution)
@@ -121,6 +134,9 @@ class Simulation:
                 gather = SpecGather(dev) if speculate else make_gather(dev)
         self.gather = gather
         self.speculate = bool(speculate)
+        if self.high_interest is not None:
+            self.w_high = (h_max * self.tan) ** 2 * math.pi if w_high is None else float(w_high)
+            ctx.set_regions(*self.high_interest, w_high=self.w_high)
         if fire is not None:
             ctx.set_points_records(fire.initial_points())
         elif firepoints is not None:
@@ -131,6 +147,30 @@ class Simulation:
         self.t = 0
         self.outputs = []
         self.records = []
+
+    @staticmethod
+    def _boxes(high_interest):
+        """None, True (the module's boxes) or (x_LB, x_UB, y_LB, y_UB) as four equal-length lists."""
+        if high_interest is None or high_interest is False:
+            return None
+        if high_interest is True:
+            return (list(x_LB), list(x_UB), list(y_LB), list(y_UB))
+        if len(high_interest) != 4:
+            raise ValueError("high_interest must be (x_LB, x_UB, y_LB, y_UB)")
+        b = tuple([float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64)).ravel()]
+                  for q in high_interest)
+        if len({len(q) for q in b}) != 1 or not b[0]:
+            raise ValueError("high_interest: x_LB, x_UB, y_LB, y_UB must be non-empty and of equal length")
+        return b
+
+    def percentage_covered(self) -> float:
+        """src/FullSimulation.jl:537-557, "Percentage of Area Covered": 100 - uncovered/total*100
+        over the points strictly inside the boxes: total over every point ever pushed, uncovered
+        over what is left in the list now. total = 0: NaN (Julia's 0/0)."""
+        if self.high_interest is None:
+            raise ValueError("percentage_covered needs high_interest")
+        total = self.ctx.regions_ingested()[1]
+        return percentage_covered(self.ctx.region_stats()["any_count"], total)
 
     def step(self) -> dict:
         ctx, N = self.ctx, self.N
@@ -150,7 +190,7 @@ class Simulation:
         kept = ctx.remove_covered(drone_locs)                            # :61
         t2 = time.perf_counter()
         if t != 1:
-            r_max_update(drone_locs, self.r_max, N)                      # :64-76
+            r_max_update(drone_locs, self.r_max, N, self.high_interest)  # :64-76
         if t < 3:                                                        # :82-84
             single_input = drone_locs
         else:
@@ -197,6 +237,10 @@ class Simulation:
                    input=single_input)
         if self.attribution:   # on the step's (post-removal) list
             rec["owned"], rec["exclusive"], _ = ctx.area_by_disk(x_out)
+        if self.high_interest is not None:   # :537-557, on the step's (post-removal) list
+            rec["hi_total"] = ctx.regions_ingested()[1]
+            rec["hi_uncovered"] = ctx.region_stats()["any_count"]
+            rec["hi_percentage"] = percentage_covered(rec["hi_uncovered"], rec["hi_total"])
         self.records.append(rec)
         self.x_prev = x_out                                              # perfect tracking
         return rec

@@ -74,7 +74,31 @@ EXPORTS = (
     "mac_area_by_disk_f64", "mac_area_by_disk_batch_f64", "mac_area_by_disk_dev_f64",
     "mac_cons_mask_f64", "mac_cons_mask_dev_f64", "mac_poll_best_cons_f64",
     "mac_poll_best_cons_dev_f64", "mac_mads_run_cons", "mac_mads_begin_cons",
+    "mac_set_regions", "mac_regions_ingested", "mac_region_stats_f64",
 )
+
+MAC_REGIONS_MAX = 64
+
+
+def high_interest_mask(x, y, boxes) -> np.ndarray:
+    """The reference's high-interest test (src/CellFunctions.jl:42, :68; src/FullSimulation.jl:542)
+    for arrays of points: ``x < x_UB && x > x_LB && y < y_UB && y > y_LB`` (all strict) for any
+    box of ``boxes = (x_LB, x_UB, y_LB, y_UB)`` (equal-length sequences). The single host
+    restatement of the test mac_set_regions applies on the device."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    x_LB, x_UB, y_LB, y_UB = boxes
+    m = np.zeros(np.broadcast(x, y).shape, dtype=bool)
+    for xl, xu, yl, yu in zip(x_LB, x_UB, y_LB, y_UB):
+        m |= (x < xu) & (x > xl) & (y < yu) & (y > yl)
+    return m
+
+
+def percentage_covered(uncovered, total) -> float:
+    """src/FullSimulation.jl:557: 100 - (uncovered / total) * 100; total = 0 gives NaN, as Julia's
+    0/0 does (x/0 with x > 0 cannot occur: uncovered <= total)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(100 - (np.float64(uncovered) / np.float64(total)) * 100)
 
 
 class MadsParams(ctypes.Structure):
@@ -230,6 +254,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_mads_result": ([_vp, _dp, ctypes.POINTER(MadsStats)], _i32),
         "mac_mads_destroy": ([_vp], None),
         "mac_mads_best_buffer": ([_vp, _vp], _i32),
+        "mac_set_regions": ([_vp, _dp, _dp, _dp, _dp, _i32, ctypes.c_double], _i32),
+        "mac_regions_ingested": ([_vp, _i64p, _i64p], _i32),
+        "mac_region_stats_f64": ([_vp, _dp, _i64, _i64p, _dp, _i64p, _dp, _i64p, _dp], _i32),
         "mac_set_points_f32": ([_vp, _fp, _fp, _fp, _i64], _i32),
         "mac_set_points_dev_f32": ([_vp, _vp, _vp, _vp, _i64], _i32),
         "mac_area_f32": ([_vp, _fp, _i64, _dp], _i32),
@@ -373,6 +400,7 @@ class Context:
         self.device = int(device)
         self._L = L
         self._steppers = weakref.WeakSet()   # closed before the context (they use its device state)
+        self._n_boxes = 0                    # high-interest boxes set (set_regions)
         self.set_algo(algo)
         if tile_points is not None:
             self.set_option(MAC_OPT_TILE_POINTS, int(tile_points))
@@ -524,6 +552,51 @@ class Context:
         _check(self._L.mac_remove_covered_f64(self._h, _ptr(c), c.size,
                                               kept.ctypes.data_as(_i64p), ctypes.byref(m)))
         return kept[: m.value].copy()
+
+    # -- high-interest regions
+    def set_regions(self, x_LB, x_UB, y_LB, y_UB, w_high: float = float("nan")) -> None:
+        """mac_set_regions: the boxes (x_LB[b], x_UB[b]) x (y_LB[b], y_UB[b]) (the reference's
+        vectors, src/FullSimulation.jl:751-754). While they are set, every entry arriving in the
+        list strictly inside any box gets weight ``w_high`` (NaN: weights left alone) and is
+        counted (regions_ingested). Zeroes the counters; entries already in the list keep their
+        weights. No boxes: clear_regions()."""
+        b = [_f64(np.atleast_1d(v)).ravel() for v in (x_LB, x_UB, y_LB, y_UB)]
+        n = b[0].size
+        if any(v.size != n for v in b):
+            raise ValueError("x_LB, x_UB, y_LB, y_UB must have equal lengths")
+        _check(self._L.mac_set_regions(self._h, _ptr(b[0]), _ptr(b[1]), _ptr(b[2]), _ptr(b[3]), n,
+                                       float(w_high)))
+        self._n_boxes = n
+
+    def clear_regions(self) -> None:
+        _check(self._L.mac_set_regions(self._h, None, None, None, None, 0, float("nan")))
+        self._n_boxes = 0
+
+    def regions_ingested(self):
+        """mac_regions_ingested: (per-box counts, union count) of the entries that arrived inside
+        the boxes since set_points / set_regions last reset the counters."""
+        n = self._n_boxes
+        box = np.zeros(max(n, 1), dtype=np.int64)
+        tot = _i64()
+        _check(self._L.mac_regions_ingested(self._h, box.ctypes.data_as(_i64p), ctypes.byref(tot)))
+        return box[:n].copy(), int(tot.value)
+
+    def region_stats(self, circles=None) -> dict:
+        """mac_region_stats_f64 on the current list: ``box_count`` / ``box_weight`` per box,
+        ``any_count`` / ``any_weight`` for the union of the boxes (each entry once) and, with
+        ``circles`` ([x; y; r]), ``covered_count`` / ``covered_weight``: the union's entries covered
+        by at least one disk (0 without circles)."""
+        n = self._n_boxes
+        c = _f64(() if circles is None else circles).ravel()
+        bc = np.zeros(max(n, 1), dtype=np.int64)
+        bw = np.zeros(max(n, 1))
+        ac, cc = _i64(), _i64()
+        aw, cw = ctypes.c_double(), ctypes.c_double()
+        _check(self._L.mac_region_stats_f64(self._h, _ptr(c) if c.size else None, c.size,
+                                            bc.ctypes.data_as(_i64p), _ptr(bw), ctypes.byref(ac),
+                                            ctypes.byref(aw), ctypes.byref(cc), ctypes.byref(cw)))
+        return dict(box_count=bc[:n].copy(), box_weight=bw[:n].copy(), any_count=int(ac.value),
+                    any_weight=aw.value, covered_count=int(cc.value), covered_weight=cw.value)
 
     # -- objective
     def area(self, circles) -> float:

@@ -31,6 +31,9 @@
 //   cons_mask_kernel      the swarm constraints (minimum spacing cons8, altitude zone cons7), one
 //                         feasibility byte per candidate: UAVs counting-sorted by x into cells in LDS,
 //                         pairs tested up to the spacing apart; cons_argmin_kernel: the masked poll's argmin (k_cons.h)
+//   region_ingest_kernel / region_stats_kernel / region_reduce_kernel  the high-interest boxes: the
+//                         weight override and counts of arriving entries, and per-box / union / covered
+//                         counts and weights of the current list through the tile index (k_regions.h)
 // (Cross-workgroup hand-offs use agent-scope stores drained before one counter add, never a
 // device-scope fence: that fence writes back the XCD's L2 on gfx950.)
 // An entry is credited to the LOWEST-index disk covering it (exactly-once union count), so the
@@ -49,3 +52,4 @@
 #include "k_bydisk.h"
 #include "k_fiw.h"
 #include "k_cons.h"
+#include "k_regions.h"

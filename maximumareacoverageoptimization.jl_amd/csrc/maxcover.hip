@@ -297,6 +297,14 @@ struct mac_ctx {
     // setup scratch
     DevBuf keys_in, keys_out, idx_in, tmp, bbox, flags_s, flags_o, keep, sel_count, cx, cy, cw,
         cidx, circ, cdisk;
+    // high-interest regions (mac_set_regions, k_regions.h): the boxes ([x_LB | x_UB | y_LB | y_UB],
+    // kRegionsMax each; unused slots NaN) on the host and the device, the weight arriving entries
+    // inside them get (NaN: left alone), the ingest counters (per box, then the union) and the
+    // stats call's items, partials and results. n_regions = 0: off, nothing is launched
+    int n_regions = 0;
+    double reg_w_high = NAN;
+    double h_boxes[4 * kRegionsMax];
+    DevBuf rboxes, rcount, ritems, rpart, rout;
 };
 
 static void set_device(mac_ctx* ctx) { HCK(hipSetDevice(ctx->device)); }
@@ -1828,7 +1836,8 @@ void mac_ctx_destroy(mac_ctx* ctx)
     for (DevBuf* b : {&ctx->x, &ctx->y, &ctx->w, &ctx->xys, &ctx->ws, &ctx->perm, &ctx->off,
                       &ctx->keys_in, &ctx->keys_out, &ctx->idx_in, &ctx->tmp, &ctx->bbox,
                       &ctx->flags_s, &ctx->flags_o, &ctx->keep, &ctx->sel_count, &ctx->cx,
-                      &ctx->cy, &ctx->cw, &ctx->cidx, &ctx->circ, &ctx->cdisk})
+                      &ctx->cy, &ctx->cw, &ctx->cidx, &ctx->circ, &ctx->cdisk, &ctx->rboxes,
+                      &ctx->rcount, &ctx->ritems, &ctx->rpart, &ctx->rout})
         b->release();
     ctx->stamps.release();
     if (ctx->setup_stream) (void)hipStreamDestroy(ctx->setup_stream);
@@ -1885,6 +1894,23 @@ int32_t mac_set_option(mac_ctx* ctx, int32_t option, int64_t value)
     }
 }
 
+// High-interest regions on (mac_set_regions): the entries [lo, hi) that just arrived in the list-order
+// arrays are tested once, before the index is built (w_uniform and the sorted weights see the final
+// weights): inside any box they take the high-interest weight and are counted. reset: a new list
+// (the counters restart at its counts); an append adds.
+static void regions_ingest(mac_ctx* ctx, hipStream_t s, int64_t lo, int64_t hi, bool reset)
+{
+    if (ctx->n_regions == 0) return;
+    if (reset) HCK(hipMemsetAsync(ctx->rcount.p, 0, sizeof(unsigned long long) * (kRegionsMax + 1), s));
+    if (hi <= lo) return;
+    const unsigned nb = std::min<unsigned>(grid1d(hi - lo, kBlock), kRegIngestBlocks);
+    hipLaunchKernelGGL(region_ingest_kernel, dim3(nb), dim3(kBlock), 0, s, ctx->x.as<double>(),
+                       ctx->y.as<double>(), ctx->w.as<double>(), lo, hi, ctx->rboxes.as<double>(),
+                       ctx->n_regions, ctx->reg_w_high, std::isnan(ctx->reg_w_high) ? 0 : 1,
+                       ctx->rcount.as<unsigned long long>());
+    HCK(hipGetLastError());
+}
+
 static int32_t set_points_common(mac_ctx* ctx, int64_t M)
 {
     if (!ctx) return fail(MAC_E_INVAL, "null context");
@@ -1915,6 +1941,7 @@ int32_t mac_set_points_f64(mac_ctx* ctx, const double* x, const double* y, const
         HCK(hipMemcpyAsync(ctx->y.p, y, sizeof(double) * M, hipMemcpyHostToDevice, s));
         HCK(hipMemcpyAsync(ctx->w.p, w, sizeof(double) * M, hipMemcpyHostToDevice, s));
     }
+    regions_ingest(ctx, s, 0, M, true);
     build_index(ctx, s);
     return MAC_OK;
     ABI_END
@@ -1932,6 +1959,7 @@ int32_t mac_set_points_f32(mac_ctx* ctx, const float* x, const float* y, const f
     upload_widen(y, M, ctx->tmp, ctx->y.as<double>(), s);
     HCK(hipStreamSynchronize(s));
     upload_widen(w, M, ctx->tmp, ctx->w.as<double>(), s);
+    regions_ingest(ctx, s, 0, M, true);
     build_index(ctx, s);
     return MAC_OK;
     ABI_END
@@ -1948,6 +1976,7 @@ int32_t mac_set_points_dev_f32(mac_ctx* ctx, const float* d_x, const float* d_y,
     widen_async(d_x, M, ctx->x.as<double>(), s);
     widen_async(d_y, M, ctx->y.as<double>(), s);
     widen_async(d_w, M, ctx->w.as<double>(), s);
+    regions_ingest(ctx, s, 0, M, true);
     build_index(ctx, s);
     return MAC_OK;
     ABI_END
@@ -1981,6 +2010,7 @@ int32_t mac_set_points_dev_f64(mac_ctx* ctx, const double* d_x, const double* d_
         HCK(hipMemcpyAsync(ctx->y.p, d_y, sizeof(double) * M, hipMemcpyDeviceToDevice, s));
         HCK(hipMemcpyAsync(ctx->w.p, d_w, sizeof(double) * M, hipMemcpyDeviceToDevice, s));
     }
+    regions_ingest(ctx, s, 0, M, true);
     build_index(ctx, s);
     return MAC_OK;
     ABI_END
@@ -2021,6 +2051,7 @@ static int32_t append_common(mac_ctx* ctx, const void* x, const void* y, const v
         HCK(hipMemcpyAsync(ctx->w.as<double>() + M0, w, sizeof(double) * m, kind, s));
     }
     ctx->M = M0 + m;
+    regions_ingest(ctx, s, M0, M0 + m, false);
     build_index(ctx, s);
     return MAC_OK;
 }
@@ -2167,6 +2198,154 @@ int32_t mac_remove_covered_f64(mac_ctx* ctx, const double* circles, int64_t thre
         build_index(ctx, s);
     }
     if (M_out) *M_out = kept;
+    return MAC_OK;
+    ABI_END
+}
+
+// ------------------------------------------------------------------ high-interest regions
+
+int32_t mac_set_regions(mac_ctx* ctx, const double* x_lb, const double* x_ub, const double* y_lb,
+                        const double* y_ub, int32_t n_boxes, double w_high)
+{
+    ABI_BEGIN
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (n_boxes < 0 || n_boxes > kRegionsMax)
+        return fail(MAC_E_INVAL, "n_boxes = " + std::to_string(n_boxes) + " outside [0, " +
+                                     std::to_string(kRegionsMax) + "]");
+    if (n_boxes > 0 && (!x_lb || !x_ub || !y_lb || !y_ub)) return fail(MAC_E_INVAL, "null bound array");
+    set_device(ctx);
+    hipStream_t s = ctx->setup_stream;
+    HCK(hipDeviceSynchronize());
+    free_deferred(ctx);
+    if (n_boxes > 0) {
+        ctx->rboxes.reserve(sizeof(double) * 4 * kRegionsMax);
+        ctx->rcount.reserve(sizeof(unsigned long long) * (kRegionsMax + 1));
+        double hb[4 * kRegionsMax];
+        for (double& v : hb) v = NAN;
+        for (int b = 0; b < n_boxes; ++b) {
+            hb[b] = x_lb[b];
+            hb[kRegionsMax + b] = x_ub[b];
+            hb[2 * kRegionsMax + b] = y_lb[b];
+            hb[3 * kRegionsMax + b] = y_ub[b];
+        }
+        HCK(hipMemcpyAsync(ctx->rboxes.p, hb, sizeof hb, hipMemcpyHostToDevice, s));
+        HCK(hipMemsetAsync(ctx->rcount.p, 0, sizeof(unsigned long long) * (kRegionsMax + 1), s));
+        HCK(hipStreamSynchronize(s));
+        std::memcpy(ctx->h_boxes, hb, sizeof hb);
+    }
+    ctx->n_regions = n_boxes;
+    ctx->reg_w_high = w_high;
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_regions_ingested(mac_ctx* ctx, int64_t* box_count, int64_t* any_count)
+{
+    ABI_BEGIN
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (ctx->n_regions == 0) return fail(MAC_E_INVAL, "no regions set (mac_set_regions)");
+    set_device(ctx);
+    hipStream_t s = ctx->setup_stream;
+    unsigned long long h[kRegionsMax + 1];
+    HCK(hipMemcpyAsync(h, ctx->rcount.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HCK(hipStreamSynchronize(s));
+    if (box_count)
+        for (int b = 0; b < ctx->n_regions; ++b) box_count[b] = (int64_t)h[b];
+    if (any_count) *any_count = (int64_t)h[kRegionsMax];
+    return MAC_OK;
+    ABI_END
+}
+
+// The items of one stats call (k_regions.h RegItem): per box with lb < ub on both axes its tile
+// range, split into bands of G rows and nch chunks per row so that an item holds about kRegChunk
+// entries of a uniformly dense list and all items together stay under kRegItemCap.
+static int regions_plan(const mac_ctx* ctx, RegItem* it)
+{
+    const Grid& g = ctx->grid;
+    const int nb = ctx->n_regions;
+    const double* B = ctx->h_boxes;
+    int nvalid = 0;
+    for (int b = 0; b < nb; ++b)
+        nvalid += B[b] < B[kRegionsMax + b] && B[2 * kRegionsMax + b] < B[3 * kRegionsMax + b];
+    const int capb = nvalid ? kRegItemCap / nvalid : 0;   // >= 1024
+    int total = 0;
+    for (int b = 0; b < nb; ++b) {
+        RegItem& I = it[b];
+        I = RegItem{0, 0, 0, -1, 1, 1, 0, total};
+        if (!(B[b] < B[kRegionsMax + b] && B[2 * kRegionsMax + b] < B[3 * kRegionsMax + b])) continue;
+        I.tx0 = tile_of(B[b], g.gx0, g.invS, g.nTx);
+        I.tx1 = tile_of(B[kRegionsMax + b], g.gx0, g.invS, g.nTx);
+        I.ty0 = tile_of(B[2 * kRegionsMax + b], g.gy0, g.invS, g.nTy);
+        I.ty1 = tile_of(B[3 * kRegionsMax + b], g.gy0, g.invS, g.nTy);
+        const int rows = I.ty1 - I.ty0 + 1;
+        I.G = (rows + capb - 1) / capb;
+        I.nrg = (rows + I.G - 1) / I.G;
+        const double est = (double)ctx->M * ((double)(I.tx1 - I.tx0 + 1) / (double)g.nTx) *
+                           ((double)I.G / (double)g.nTy);
+        const double want = std::ceil(est / (double)kRegChunk);
+        I.nch = (int)std::max(1.0, std::min(want, (double)(capb / I.nrg)));
+        total += I.nrg * I.nch;
+    }
+    return total;
+}
+
+int32_t mac_region_stats_f64(mac_ctx* ctx, const double* circles, int64_t three_n, int64_t* box_count,
+                             double* box_weight, int64_t* any_count, double* any_weight,
+                             int64_t* covered_count, double* covered_weight)
+{
+    ABI_BEGIN
+    int32_t rc = check_common(ctx, three_n, 0);
+    if (rc) return rc;
+    if (ctx->n_regions == 0) return fail(MAC_E_INVAL, "no regions set (mac_set_regions)");
+    if (three_n > 0 && !circles) return fail(MAC_E_INVAL, "null circles");
+    const int N = (int)(three_n / 3);
+    if (N > kRegMaxDisks)
+        return fail(MAC_E_INVAL, "mac_region_stats: N = " + std::to_string(N) + " > " +
+                                     std::to_string(kRegMaxDisks) + " UAVs");
+    const int nb = ctx->n_regions;
+    std::vector<unsigned long long> hc(nb + 2, 0);
+    std::vector<double> hw(nb + 2, 0.0);
+    RegItem it[kRegionsMax];
+    const int total = ctx->M > 0 ? regions_plan(ctx, it) : 0;
+    if (total > 0) {
+        set_device(ctx);
+        hipStream_t s = ctx->setup_stream;
+        HCK(hipDeviceSynchronize());
+        free_deferred(ctx);
+        ctx->ritems.reserve(sizeof(RegItem) * kRegionsMax);
+        ctx->rpart.reserve(sizeof(RegPartial) * (size_t)total);
+        ctx->rout.reserve((sizeof(unsigned long long) + sizeof(double)) * (kRegionsMax + 2));
+        ctx->cdisk.reserve(sizeof(DiskRec) * std::max(N, 1));
+        unsigned long long* d_oc = ctx->rout.as<unsigned long long>();
+        double* d_ow = (double*)(d_oc + kRegionsMax + 2);
+        HCK(hipMemcpyAsync(ctx->ritems.p, it, sizeof(RegItem) * nb, hipMemcpyHostToDevice, s));
+        if (N > 0) {
+            ctx->circ.reserve(sizeof(double) * 3 * N);
+            HCK(hipMemcpyAsync(ctx->circ.p, circles, sizeof(double) * 3 * N, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(disk_prep_kernel, dim3(grid1d(N, 256)), dim3(256), 0, s,
+                               matrix_src(ctx->circ.as<double>(), N), N, 1, ctx->cdisk.as<DiskRec>());
+            HCK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(region_stats_kernel, dim3(grid1d(total, kWavesPerBlock)), dim3(kBlock), 0, s,
+                           ctx->xys.as<double2>(), ctx->ws.as<double>(), ctx->off.as<int32_t>(), ctx->grid,
+                           ctx->rboxes.as<double>(), nb, ctx->ritems.as<RegItem>(), total,
+                           ctx->cdisk.as<DiskRec>(), N, ctx->rpart.as<RegPartial>());
+        HCK(hipGetLastError());
+        hipLaunchKernelGGL(region_reduce_kernel, dim3(nb + 1), dim3(kBlock), 0, s,
+                           ctx->rpart.as<RegPartial>(), ctx->ritems.as<RegItem>(), nb, total, d_oc, d_ow);
+        HCK(hipGetLastError());
+        HCK(hipMemcpyAsync(hc.data(), d_oc, sizeof(unsigned long long) * (nb + 2), hipMemcpyDeviceToHost, s));
+        HCK(hipMemcpyAsync(hw.data(), d_ow, sizeof(double) * (nb + 2), hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+    }
+    for (int b = 0; b < nb; ++b) {
+        if (box_count) box_count[b] = (int64_t)hc[b];
+        if (box_weight) box_weight[b] = hw[b];
+    }
+    if (any_count) *any_count = (int64_t)hc[nb];
+    if (any_weight) *any_weight = hw[nb];
+    if (covered_count) *covered_count = (int64_t)hc[nb + 1];
+    if (covered_weight) *covered_weight = hw[nb + 1];
     return MAC_OK;
     ABI_END
 }
