@@ -792,7 +792,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
                         case 3: poll_hot<3, kFwWaves>(s32, ng, wid, sa, sb, st, ns, h, bmin); break;
                         default: poll_hot<4, kFwWaves>(s32, ng, wid, sa, sb, st, ns, h, bmin); break;
                         }
-                        const double wu = kCounts ? 1.0 : sw[0];
+                        // (a chunk with no kept entry wrote no sw[0]: 0 x a stale word could be NaN)
+                        const double wu = kCounts ? 1.0 : n > 0 ? sw[0] : 0.0;
 #pragma unroll
                         for (int u = 0; u < kPollSlots; ++u) {
                             const float hc = (u & 1) ? h[u >> 1].y : h[u >> 1].x;

@@ -449,7 +449,8 @@ __device__ __forceinline__ void coverage_poll_body(
                     default: poll_hot<4>(s32, ng, wid, sa, sb, st, ns, h, bmin); break;
                     }
                     // counts < 2^24: exact in fp32 when no entry is in the band
-                    const double wu = sw[0];
+                    // (a chunk with no kept entry wrote no sw[0]: 0 x a stale word could be NaN)
+                    const double wu = n > 0 ? sw[0] : 0.0;
 #pragma unroll
                     for (int u = 0; u < kPollSlots; ++u) {
                         if (!(live & (1u << u))) continue;

@@ -498,7 +498,13 @@ static Grid choose_grid(double xmn, double xmx, double ymn, double ymx, int64_t 
         g.nTy = 1;
         return g;
     }
-    const double W = xmx - xmn, H = ymx - ymn;
+    // A finite box whose span overflows counts as DBL_MAX wide: tile_of sends every entry further
+    // than that from the origin ((v - g0) = inf) to the last tile, and tile_span's error term
+    // overflows with the disk's bound, which gives the whole axis.
+    const double W = std::min(xmx - xmn, kDblMax), H = std::min(ymx - ymn, kDblMax);
+    // The pitch stays within [2^-1020, 2^1020]: S and 1 / S are both normal doubles, whatever the
+    // span (a subnormal W would otherwise give invS = inf, a DBL_MAX one a subnormal invS).
+    constexpr double kMinPitch = 0x1p-1020, kMaxPitch = 0x1p1020;
     double S;
     if (W > 0 && H > 0)
         S = std::sqrt(W * H * (double)ppt / (double)M);
@@ -507,6 +513,7 @@ static Grid choose_grid(double xmn, double xmx, double ymn, double ymx, int64_t 
     else
         S = 1.0;
     if (!(S > 0) || !std::isfinite(S)) S = 1.0;
+    S = std::min(std::max(S, kMinPitch), kMaxPitch);
     // cap the tile count (int32 keys, offsets memory): at most max(4M, 2^20) tiles, 2^28 total
     const double cap = std::min(268435456.0, std::max(4.0 * (double)M, 1048576.0));
     for (int it = 0; it < 64; ++it) {
@@ -514,17 +521,21 @@ static Grid choose_grid(double xmn, double xmx, double ymn, double ymx, int64_t 
         if (nx * ny <= cap && nx < 1e8 && ny < 1e8) break;
         S *= 1.5;
     }
-    {   // still too many tiles (e.g. a bbox of 1e300 m): at most 1024 x 1024
+    {   // still too many tiles (e.g. a bbox of 1e300 m): at most 1001 x 1001
         const double nx = std::floor(W / S) + 1.0, ny = std::floor(H / S) + 1.0;
         if (!(nx * ny <= cap) || !(nx < 1e8) || !(ny < 1e8)) S = std::max(W, H) / 1000.0;
-        if (!(S > 0) || !std::isfinite(S)) S = kDblMax;
+        S = std::min(std::max(S, kMinPitch), kMaxPitch);
     }
+    // The counts come from span * invS (what tile_of computes), the loop's from span / S: where the
+    // two round apart at the cap, one more step.
+    auto count = [](double span, double inv) { return std::min(std::floor(span * inv) + 1.0, 1e8); };
+    while (S < kMaxPitch && count(W, 1.0 / S) * count(H, 1.0 / S) > cap) S = std::min(S * 1.5, kMaxPitch);
     g.gx0 = xmn;
     g.gy0 = ymn;
     g.S = S;
     g.invS = 1.0 / S;
-    g.nTx = (int)std::min(std::floor(W * g.invS) + 1.0, 1e8);
-    g.nTy = (int)std::min(std::floor(H * g.invS) + 1.0, 1e8);
+    g.nTx = (int)count(W, g.invS);
+    g.nTy = (int)count(H, g.invS);
     if (g.nTx < 1) g.nTx = 1;
     if (g.nTy < 1) g.nTy = 1;
     return g;
@@ -1063,6 +1074,15 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             bits_on = ctx->shared_mode == MAC_SHARED_BITS ? 2
                     : ctx->shared_mode == MAC_SHARED_FP64 ? 0
                     : dc_max > kBitsMinDisks ? 1 : 0;
+            // Both passes stage an entry as its fp32 offset (u, v) from a region's centre with
+            // q = u u + v v, and q = +inf marks "no entry" (k_or.h, k_bits.h: outside the box, past
+            // the list, non-finite). A finite entry must therefore keep q finite: |u|, |v| below
+            // 2^63. Offsets are bounded by the grid's extent, so on a grid of 2^62 or more (a far
+            // outlier sets the pitch: the centre of the tile that holds the rest of the list lies
+            // S / 2 away from it) finite entries would drop out of the unions, and the poll
+            // kernel's fp64 jobs take every disk there.
+            const Grid& gr = ctx->grid;
+            if (!(((double)std::max(gr.nTx, gr.nTy) + 1.0) * gr.S < 0x1p62)) bits_on = 0;
             // equal weights: the union pass (k_or.h), whose jobs walk_setup lists with the upper
             // neighbour boxes; weighted lists: the bit-word kernel (k_bits.h)
             OrSetup orj{};
@@ -1602,6 +1622,33 @@ int32_t mac_diag_read(uint64_t* out, int64_t n)
     return MAC_OK;
 }
 #endif
+
+// host only, every build (not declared in maxcover.h): the tile grid build_index chooses for a
+// list of M entries with this bounding box of its finite entries; out = {S, invS, nTx, nTy}
+int32_t mac_diag_grid(double xmn, double xmx, double ymn, double ymx, int64_t M, int32_t tile_points,
+                      double* out)
+{
+    if (!out || tile_points < 1) return MAC_E_INVAL;
+    const Grid g = choose_grid(xmn, xmx, ymn, ymx, M, tile_points);
+    out[0] = g.S;
+    out[1] = g.invS;
+    out[2] = (double)g.nTx;
+    out[3] = (double)g.nTy;
+    return MAC_OK;
+}
+
+// host only, every build (not declared in maxcover.h): predicate.h's tile_of of the coordinate c and
+// tile_span of the disk (c, r) along one axis of a grid; out = {tile_of, span found (0 / 1), lo, hi}
+int32_t mac_diag_tiles(double c, double r, double g0, double invS, int32_t n, int32_t* out)
+{
+    if (!out || n < 1) return MAC_E_INVAL;
+    int lo = -1, hi = -1;
+    out[0] = tile_of(c, g0, invS, n);
+    out[1] = tile_span(c, r, g0, invS, n, lo, hi) ? 1 : 0;
+    out[2] = lo;
+    out[3] = hi;
+    return MAC_OK;
+}
 
 const char* mac_last_error(void) { return g_last_error.c_str(); }
 
