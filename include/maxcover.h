@@ -387,6 +387,41 @@ void mac_mads_destroy(mac_mads* m);
  * host-to-device copy per iteration (dist.DeviceGather). */
 int32_t mac_mads_best_buffer(mac_mads* m, void* d_best16);
 
+/* The poll kind of the native driver. The reference's CustomPoll "returns directions only in the xy
+ * plane. To be used when no height changes need to be explored (i.e. when height constraint is
+ * already being satisfied)" (src/TDM_STATIC_opt.jl:15-44, selected at :122): the objective charges
+ * 1e5 |R_i - r_max_i| (:92), so once the radii sit at their best granular value every candidate that
+ * touches a radius loses, and a full poll's columns are dense below the diagonal. MAC_POLL_XY is that
+ * capability on this driver's LTMADS restatement (not the reference's N = 3 ring of 20 directions):
+ * with n_p = 2N polled variables x_0..x_{N-1}, y_0..y_{N-1}, every iteration draws the basis
+ * B = L[rp][:, cp] of size n_p from the same splitmix64 stream (n_p + n_p(n_p-1)/2 + 2 n_p values
+ * per iteration) and polls the 2 n_p = 4N candidates x + E B[:, k] (k < n_p), x - E B[:, k - n_p]
+ * (k >= n_p), E putting B's rows on the first 2N variables; a candidate's radii are the incumbent's
+ * doubles copied bit for bit, so x_out's radii equal x0's. evaluations grows by 2 n_p per iteration,
+ * shards are [lo, hi) within [0, 2 n_p], best_idx is poll-wide in [0, 2 n_p), and the whole-poll
+ * rejection (rejected_polls) runs over the n_p polled variables. cons3, the mac_cons mask, the chain
+ * routing and the success / failure rule are the full poll's. */
+#define MAC_POLL_XYR 0   /* every variable (default) */
+#define MAC_POLL_XY  1   /* x and y only: src/TDM_STATIC_opt.jl:15-44 */
+typedef struct mac_mads_opts {
+    int32_t poll_vars;     /* MAC_POLL_XYR or MAC_POLL_XY */
+    int32_t reserved[3];   /* 0 */
+} mac_mads_opts;           /* 16 B */
+/* mac_mads_run_cons / mac_mads_begin_cons with options (src/TDM_STATIC_opt.jl:118-169, the poll type
+ * of :122). opts = NULL or poll_vars = MAC_POLL_XYR: the _cons call itself (cons = NULL: the plain
+ * call) — the same launches, outputs and statistics. An unknown poll_vars, a non-zero reserved word
+ * or a shard outside [0, 2 n_p]: MAC_E_INVAL, nothing written (*out cleared, as mac_mads_begin_cons
+ * does). A stepper begun under MAC_POLL_XY polls xy in every call that takes it (mac_mads_poll,
+ * _update, _poll_ahead, _advance, _result, _best_buffer). */
+int32_t mac_mads_run_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* params, double* x_out, mac_mads_stats* stats,
+                          const mac_cons* cons, const mac_mads_opts* opts);
+int32_t mac_mads_begin_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
+                            mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts);
+
 /* fp32 candidates (config 3's "fp32" caller path; SURVEY 8(b) "*_f32: coords f32, accum f64"):
  * the candidate matrix (and prev) are uploaded as floats and widened exactly on the device;
  * coverage is then the reference's fp64 predicate on those doubles, areas accumulate in fp64 /

@@ -18,7 +18,7 @@ is what the parity tests exercise. See INTEGRATION.md.
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MacCons, cons_mask,
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacCons, cons_mask,
        set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
@@ -355,25 +355,57 @@ struct MadsStats
 end
 
 """
-mads_run(x0, r_max, ctx; prev, d_lim, tan_half_fov, n_iter, ell0, ell_max, seed, cons) — the whole
+MadsOpts — mac_mads_opts (include/maxcover.h), 16 bytes: the native driver's poll kind, MAC_POLL_XYR
+(0: every variable) or MAC_POLL_XY (1: x and y only, the radii held; the reference's CustomPoll,
+src/TDM_STATIC_opt.jl:15-44); the reserved words are 0.
+"""
+struct MadsOpts
+    poll_vars::Int32
+    reserved1::Int32
+    reserved2::Int32
+    reserved3::Int32
+end
+MadsOpts(poll_vars::Symbol) = MadsOpts(poll_vars === :xyr ? Int32(0) : poll_vars === :xy ? Int32(1) :
+                                       throw(ArgumentError("poll_vars must be :xyr or :xy")),
+                                       Int32(0), Int32(0), Int32(0))
+
+"""
+mads_run(x0, r_max, ctx; prev, d_lim, tan_half_fov, n_iter, ell0, ell_max, seed, cons, poll_vars) — the whole
 granular-MADS loop inside libmaxcover (complete LTMADS poll generated on the device, cons3 as
 extreme barrier): the batched stand-in for TDM_STATIC_opt.optimize (src/TDM_STATIC_opt.jl:118-169).
 With `cons::MacCons` (mac_mads_run_cons) every poll also applies cons8 / cons7 on the device — the
 `cons_ext` slot of the reference's [cons_ext, cons3] — and the candidates they reject are not
-evaluated; `nothing` keeps the plain call. Returns (x, stats::MadsStats).
+evaluated; `nothing` keeps the plain call. `poll_vars = :xy` (mac_mads_run_opts, MAC_POLL_XY) polls
+x and y only — 4N candidates per poll from a basis of size 2N, the radii of `x` equal to `x0`'s bit
+for bit — for the steps where "no height changes need to be explored" (src/TDM_STATIC_opt.jl:15-44);
+`:xyr`, the default, is the calls above. Like the rest of this shim, the `poll_vars` path has not been
+executed here. Returns (x, stats::MadsStats).
 """
 function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                   penalty::Float64 = 1e5, prev::Union{Nothing,Vector{Float64}} = nothing,
                   d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
                   n_iter::Integer = 100, ell0::Integer = 2, ell_max::Integer = 6,
-                  seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing)
+                  seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing,
+                  poll_vars::Symbol = :xyr)
+    opts = MadsOpts(poll_vars)
     x = similar(x0)
     prm = Ref(MadsParams(n_iter, ell0, ell_max, UInt64(seed)))
     st = Ref{MadsStats}()
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
     GC.@preserve prev d_lim begin
-        if cons === nothing
+        if opts.poll_vars != 0
+            rcons = cons === nothing ? nothing : Ref(cons)   # (kept alive across the call)
+            GC.@preserve rcons begin
+                pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)
+                check(ccall((:mac_mads_run_opts, libmaxcover), Int32,
+                            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                             Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats},
+                             Ptr{MacCons}, Ref{MadsOpts}),
+                            ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st,
+                            pcons, Ref(opts)))
+            end
+        elseif cons === nothing
             check(ccall((:mac_mads_run, libmaxcover), Int32,
                         (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
                          Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats}),

@@ -62,6 +62,15 @@ def cons3_ok(prev: np.ndarray, x: np.ndarray, d_lim: np.ndarray) -> bool:
     return True
 
 
+def auto_poll_vars(R, r_max) -> str:
+    """The per-step choice of ``Simulation(poll_vars="auto")``: "xy" when every |R_i - r_max_i| <= 0.5
+    at the MADS input — no +-1 step of a radius on the granular mesh then lowers the objective's
+    1e5 |R_i - r_max_i| (src/TDM_STATIC_opt.jl:92), the reference CustomPoll's "height constraint is
+    already being satisfied" (:15-44) — else "xyr". Needs no GPU."""
+    d = np.abs(np.asarray(R, dtype=np.float64) - np.asarray(r_max, dtype=np.float64))
+    return "xy" if bool(np.all(d <= 0.5)) else "xyr"
+
+
 def split_cons_ext(cons_ext):
     """The ``cons_ext`` slot of the reference's MADS call ([cons_ext, cons3], :86, :97) as the one
     mac_cons mapping the native driver takes (TDM_Constraints.merge_mac_cons; None: nothing on).
@@ -93,13 +102,21 @@ class Simulation:
     (h_max*tan(FOV/2))^2*pi, src/CellFunctions.jl:44) on the device, the r_max rule reads the same
     boxes, and each record gains ``hi_total`` (points ever pushed inside the boxes), ``hi_uncovered``
     (those left in the list after the step's removal) and ``hi_percentage`` (:537-557). Every rank of
-    a multi-GPU run sets the same regions; nothing is exchanged. None: no region call is made."""
+    a multi-GPU run sets the same regions; nothing is exchanged. None: no region call is made.
+    ``poll_vars``: "xyr" (every variable, the default), "xy" (x and y only, the radii held:
+    MAC_POLL_XY, the reference's CustomPoll, src/TDM_STATIC_opt.jl:15-44) or "auto" (per step, on the
+    host after the r_max rule: auto_poll_vars); under "xy" and "auto" each record gains ``poll_vars``,
+    what the step used (the default's records keep the keys they had)."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
                  shard=None, gather=None, speculate: bool | None = None, device=None,
-                 attribution: bool = False, cons_ext=(), high_interest=None, w_high=None):
+                 attribution: bool = False, cons_ext=(), high_interest=None, w_high=None,
+                 poll_vars: str = "xyr"):
+        if poll_vars not in ("xyr", "xy", "auto"):
+            raise ValueError(f"poll_vars must be 'xyr', 'xy' or 'auto', not {poll_vars!r}")
+        self.poll_vars = poll_vars
         self.ctx = ctx
         self.high_interest = self._boxes(high_interest)
         if self.high_interest is None and w_high is not None:
@@ -201,6 +218,11 @@ class Simulation:
                   ell0=self.ell0, ell_max=self.ell_max, seed=self.seed + t)
         if self.cons is not None:
             kw["cons"] = self.cons
+        pvars = self.poll_vars
+        if pvars == "auto":
+            pvars = auto_poll_vars(single_input[2 * N:], self.r_max)
+        if pvars != "xyr":   # (the default: the calls as they were)
+            kw["poll_vars"] = pvars
         if self.shard is None or self.shard[1] == 1:
             x_out, st = ctx.mads_run(single_input, self.r_max, 1e5, **kw)
         elif self.speculate:
@@ -212,7 +234,8 @@ class Simulation:
                 stepper.close()
         else:
             from .dist import mads_loop, shard_range
-            lo, hi = shard_range(2 * single_input.size, *self.shard)
+            n_polled = single_input.size if pvars == "xyr" else 2 * N
+            lo, hi = shard_range(2 * n_polled, *self.shard)
             stepper = ctx.mads_stepper(single_input, self.r_max, 1e5, shard=(lo, hi), **kw)
             try:
                 x_out, st = mads_loop(stepper, self.gather)
@@ -235,6 +258,8 @@ class Simulation:
                    mads_host_s={k: float(st.get(k, 0.0)) for k in
                                 ("host_enqueue_s", "host_perm_s", "wait_s", "host_post_s")},
                    input=single_input)
+        if self.poll_vars != "xyr":   # (the default's records are what they were)
+            rec["poll_vars"] = pvars
         if self.attribution:   # on the step's (post-removal) list
             rec["owned"], rec["exclusive"], _ = ctx.area_by_disk(x_out)
         if self.high_interest is not None:   # :537-557, on the step's (post-removal) list

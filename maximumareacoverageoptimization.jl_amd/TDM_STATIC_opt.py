@@ -94,19 +94,44 @@ class MADSResult:
         self.status = Status()
 
 
+def polled_count(n: int, poll_vars: str = "xyr") -> int:
+    """n_p, the variables a poll moves: all n = 3N ("xyr"), or x_0..x_{N-1}, y_0..y_{N-1} ("xy": the
+    reference's CustomPoll, "directions only in the xy plane", src/TDM_STATIC_opt.jl:15-44)."""
+    if poll_vars == "xyr":
+        return n
+    if poll_vars == "xy":
+        return 2 * (n // 3)
+    raise ValueError(f"poll_vars must be 'xyr' or 'xy', not {poll_vars!r}")
+
+
+def poll_matrix(x: np.ndarray, B: np.ndarray) -> np.ndarray:
+    """The 2 n_p candidates of a poll around x with the basis B (n_p x n_p): x + E B[:, k], then
+    x - E B[:, k], E putting B's rows on the first n_p variables; the others (the radii of an
+    xy-only poll) are x's doubles copied."""
+    n_p = B.shape[0]
+    if n_p == x.size:
+        return np.concatenate([x[None, :] + B.T, x[None, :] - B.T], axis=0)
+    X = np.repeat(x[None, :], 2 * n_p, axis=0)
+    X[:n_p, :n_p] = x[None, :n_p] + B.T
+    X[n_p:, :n_p] = x[None, :n_p] - B.T
+    return X
+
+
 def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-         seed: int = 20250216) -> MADSResult:
+         seed: int = 20250216, poll_vars: str = "xyr") -> MADSResult:
     """Granular MADS, complete poll over D = [B, -B] (B an LTMADS-style integer basis whose
     entries are bounded by 2^ell), extreme barrier on cons_ext. Success: ell <- min(ell+1,
     ell_max) (larger steps); failure: ell <- ell-1; stop when ell < 0 (below the granularity
     1.0 of every variable, src/TDM_STATIC_opt.jl:131-137) or after N_iter iterations (:126).
     With a batched objective (``obj.poll``), cons3 and the constraints carrying ``mac_cons`` data
     (TDM_Constraints.create_cons8 / create_cons7) are applied on the device inside the poll; the
-    iterates are the ones the same constraints give as plain host callables."""
+    iterates are the ones the same constraints give as plain host callables.
+    ``poll_vars="xy"``: the basis is drawn over the n_p = 2N variables x, y (same stream, n := n_p)
+    and the radii are held (MAC_POLL_XY, include/maxcover.h)."""
     t0 = time.perf_counter()
     res = MADSResult()
     x = np.asarray(input, dtype=np.float64).copy()
-    n = x.size
+    n = polled_count(x.size, poll_vars)
     rng = SplitMix64(seed)
     cons = list(cons_ext)
 
@@ -127,7 +152,7 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
     while it < N_iter and ell >= 0:
         it += 1
         B = ltmads_basis(n, ell, rng).astype(np.float64)
-        X = np.concatenate([x[None, :] + B.T, x[None, :] - B.T], axis=0)
+        X = poll_matrix(x, B)
         n3 = sum(bool(cons3(v)) for v in X) if cons3 is not None else X.shape[0]
         res.status.cons3_passed += n3
         res.status.cons3_empty_polls += n3 == 0
@@ -171,12 +196,13 @@ class PollStepper:
     driven by ``dist.mads_loop``: the poll sequence of ``mads`` (same stream, same update rule),
     of which this stepper evaluates only the shard [lo, hi) of every poll's 2n candidates, through
     ``poll_fn(X_shard) -> (best_obj, best_local_index)`` (index -1: nothing feasible). Every rank
-    draws the whole basis, so all ranks stay at the same stream position."""
+    draws the whole basis, so all ranks stay at the same stream position. ``poll_vars``: as
+    ``mads`` (n = n_p, the polled variables)."""
 
     def __init__(self, x0, f0: float, poll_fn, N_iter: int = 100, ell0: int = 2,
-                 ell_max: int = 6, seed: int = 20250216, shard=None):
+                 ell_max: int = 6, seed: int = 20250216, shard=None, poll_vars: str = "xyr"):
         self.x = np.asarray(x0, dtype=np.float64).copy()
-        self.n = self.x.size
+        self.n = polled_count(self.x.size, poll_vars)
         self.f = float(f0)
         self.poll_fn = poll_fn
         self.N_iter, self.ell, self.ell_max = N_iter, ell0, ell_max
@@ -191,7 +217,7 @@ class PollStepper:
             return True, np.inf, -1
         self.it += 1
         B = ltmads_basis(self.n, self.ell, self.rng).astype(np.float64)
-        self._X = np.concatenate([self.x[None, :] + B.T, self.x[None, :] - B.T], axis=0)
+        self._X = poll_matrix(self.x, B)
         Xs = self._X[self.lo:self.hi]
         if Xs.shape[0] == 0:
             return False, np.inf, -1
@@ -217,7 +243,7 @@ class PollStepper:
         with np.errstate(over="ignore"):
             rng.state = self.rng.state + np.uint64(ahead * self._draws()) * np.uint64(0x9E3779B97F4A7C15)
         B = ltmads_basis(self.n, self.ell - ahead, rng).astype(np.float64)
-        return np.concatenate([self.x[None, :] + B.T, self.x[None, :] - B.T], axis=0)
+        return poll_matrix(self.x, B)
 
     def poll_ahead(self, ahead: int):
         """(done, best_obj, best_idx, feasible): feasible is not tracked here (0)."""

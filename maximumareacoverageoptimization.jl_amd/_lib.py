@@ -75,6 +75,7 @@ EXPORTS = (
     "mac_cons_mask_f64", "mac_cons_mask_dev_f64", "mac_poll_best_cons_f64",
     "mac_poll_best_cons_dev_f64", "mac_mads_run_cons", "mac_mads_begin_cons",
     "mac_set_regions", "mac_regions_ingested", "mac_region_stats_f64",
+    "mac_mads_run_opts", "mac_mads_begin_opts",
 )
 
 MAC_REGIONS_MAX = 64
@@ -116,6 +117,24 @@ class MadsStats(ctypes.Structure):
                 ("wait_s", ctypes.c_double), ("host_post_s", ctypes.c_double),
                 ("feasible_evaluations", ctypes.c_int64), ("rejected_polls", ctypes.c_int64),
                 ("successes", ctypes.c_int64), ("slot_fallbacks", ctypes.c_int64)]
+
+
+MAC_POLL_XYR = 0
+MAC_POLL_XY = 1
+POLL_VARS = {"xyr": MAC_POLL_XYR, "xy": MAC_POLL_XY}
+
+
+class MadsOpts(ctypes.Structure):
+    """mac_mads_opts (include/maxcover.h): the native driver's poll kind (16 B, reserved = 0)."""
+    _fields_ = [("poll_vars", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+def poll_vars_code(poll_vars) -> int:
+    """MAC_POLL_XYR / MAC_POLL_XY from "xyr" / "xy" (ValueError otherwise)."""
+    try:
+        return POLL_VARS[poll_vars]
+    except (KeyError, TypeError):
+        raise ValueError(f"poll_vars must be 'xyr' or 'xy', not {poll_vars!r}") from None
 
 
 class FireParams(ctypes.Structure):
@@ -235,6 +254,12 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_mads_begin_cons": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                                  ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
                                  ctypes.POINTER(Cons)], _i32),
+        "mac_mads_run_opts": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                               ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats),
+                               ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts)], _i32),
+        "mac_mads_begin_opts": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                                 ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
+                                 ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts)], _i32),
         "mac_append_points_dev_f64": ([_vp, _vp, _vp, _vp, _i64], _i32),
         "mac_fire_last_error": ([], ctypes.c_char_p),
         "mac_fire_thresholds": ([ctypes.POINTER(FireParams), _dp], None),
@@ -790,11 +815,13 @@ class Context:
     # -- native MADS driver
     def mads_run(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                  tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-                 seed: int = 20250216, cons=None):
+                 seed: int = 20250216, cons=None, poll_vars: str = "xyr"):
         """mac_mads_run: the whole MADS loop in libmaxcover (candidates generated on the device).
         ``cons`` (a Cons, or anything make_cons takes, e.g. TDM_Constraints.merge_mac_cons's
         mapping): the swarm constraints every poll applies on the device (mac_mads_run_cons); None
-        keeps the plain call. Returns (x, stats dict)."""
+        keeps the plain call. ``poll_vars``: "xyr" polls every variable (the calls above), "xy"
+        x and y only with the radii held (mac_mads_run_opts, MAC_POLL_XY). Returns (x, stats dict)."""
+        pvars = poll_vars_code(poll_vars)
         x = _f64(x0)
         rm = _f64(r_max)
         pv = _f64(prev) if prev is not None else None
@@ -806,7 +833,11 @@ class Context:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), _ptr(out), ctypes.byref(st))
         cs = make_cons(cons)
-        if cs is None:
+        if pvars != MAC_POLL_XYR:
+            op = MadsOpts(pvars)
+            _check(self._L.mac_mads_run_opts(*args, ctypes.byref(cs) if cs is not None else None,
+                                             ctypes.byref(op)))
+        elif cs is None:
             _check(self._L.mac_mads_run(*args))
         else:
             _check(self._L.mac_mads_run_cons(*args, ctypes.byref(cs)))
@@ -815,12 +846,13 @@ class Context:
     def mads_stepper(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                      tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2,
                      ell_max: int = 6, seed: int = 20250216, shard=None,
-                     cons=None) -> "MadsStepper":
+                     cons=None, poll_vars: str = "xyr") -> "MadsStepper":
         """mac_mads_begin: the native loop one poll at a time over the candidate shard
-        ``shard`` = (lo, hi) of each poll's 2n candidates (None: the whole poll). ``cons``: as
-        mads_run's (mac_mads_begin_cons; every rank of a sharded loop passes the same one)."""
+        ``shard`` = (lo, hi) of each poll's 2 n_p candidates (None: the whole poll). ``cons``: as
+        mads_run's (mac_mads_begin_cons; every rank of a sharded loop passes the same one).
+        ``poll_vars``: as mads_run's (n_p = 3N for "xyr", 2N for "xy": mac_mads_begin_opts)."""
         st = MadsStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
-                         ell_max, seed, shard, cons)
+                         ell_max, seed, shard, cons, poll_vars)
         self._steppers.add(st)
         return st
 
@@ -1016,10 +1048,13 @@ class Context:
 class MadsStepper:
     """mac_mads_begin / _poll / _update / _result (include/maxcover.h): poll() -> (done,
     best_obj, best_idx) over this stepper's shard; update(obj, idx) with the best over all
-    shards; result() -> (x, stats). dist.mads_loop drives it."""
+    shards; result() -> (x, stats). dist.mads_loop drives it. ``n_polled`` is n_p (3N, or 2N under
+    poll_vars="xy") and ``candidates`` = 2 n_p, every poll's candidate count; the default shard is
+    (0, candidates)."""
 
     def __init__(self, ctx: Context, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter,
-                 ell0, ell_max, seed, shard, cons=None):
+                 ell0, ell_max, seed, shard, cons=None, poll_vars: str = "xyr"):
+        pvars = poll_vars_code(poll_vars)
         self._L = ctx._L
         self._ctx = ctx   # keeps the context alive while the stepper lives
         x = _f64(x0)
@@ -1027,7 +1062,10 @@ class MadsStepper:
         pv = _f64(prev) if prev is not None else None
         dl = _f64(d_lim) if d_lim is not None else None
         self.n = x.size
-        lo, hi = (0, 2 * x.size) if shard is None else (int(shard[0]), int(shard[1]))
+        self.poll_vars = poll_vars
+        self.n_polled = x.size if pvars == MAC_POLL_XYR else 2 * (x.size // 3)
+        self.candidates = 2 * self.n_polled
+        lo, hi = (0, self.candidates) if shard is None else (int(shard[0]), int(shard[1]))
         self.shard = (lo, hi)
         prm = MadsParams(int(n_iter), int(ell0), int(ell_max), int(seed) & (2**64 - 1))
         h = _vp()
@@ -1035,7 +1073,11 @@ class MadsStepper:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), lo, hi, ctypes.byref(h))
         cs = make_cons(cons)
-        if cs is None:
+        if pvars != MAC_POLL_XYR:
+            op = MadsOpts(pvars)
+            _check(self._L.mac_mads_begin_opts(*args, ctypes.byref(cs) if cs is not None else None,
+                                               ctypes.byref(op)))
+        elif cs is None:
             _check(self._L.mac_mads_begin(*args))
         else:
             _check(self._L.mac_mads_begin_cons(*args, ctypes.byref(cs)))

@@ -60,6 +60,7 @@ struct FinBest {
     int* hint;
     int* hint_host;
     int nhint;
+    int np;                    // (pipelined loop) polled variables, the first np of x (0: all n)
     // a stepper's cumulative count of candidates that passed cons3 (k_prep.h PrepArgs.feas; null:
     // none): the last block also writes it to the mirror's word 4 (a 64-B slot), under the check
     const unsigned long long* feas;
@@ -83,10 +84,14 @@ __host__ __device__ __forceinline__ uint64_t mirror_check(uint64_t o, uint64_t i
 // acceptance: a strictly better objective moves the incumbent and coarsens the mesh, else the mesh
 // is refined), with the same ltmads_entry values and per-variable adds, so the pipelined loop visits
 // the stepper's incumbents bit for bit. ell, f: the state before the poll.
+// kXY: an xy-only poll (fb.np polled variables; selected at compile time, so the full poll's
+// finalize is the code it was).
+template <bool kXY = false>
 __device__ __forceinline__ void mads_step(const FinBest& fb, double bo, int64_t gidx, int ell, double f)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int n = fb.n;
+    const int np = kXY ? fb.np : n;   // the basis's size: an xy-only poll leaves x[np..n) as it is
     const double* __restrict__ x = fb.x;
     double* __restrict__ xn = fb.x_next;
     const bool better = gidx >= 0 && bo < f;
@@ -94,8 +99,8 @@ __device__ __forceinline__ void mads_step(const FinBest& fb, double bo, int64_t 
     // (a load-then-store loop was one memory round trip per variable: ~10 us at n = 1536)
     constexpr int kB = 8;
     const int64_t b = (int64_t)1 << ell;
-    const bool plus = gidx < n;
-    const int c = better ? fb.cp[plus ? (int)gidx : (int)gidx - n] : 0;
+    const bool plus = gidx < np;
+    const int c = better ? fb.cp[plus ? (int)gidx : (int)gidx - np] : 0;
     for (int v0 = lane; v0 < n; v0 += kB * kWave) {
         double xv[kB];
         int rv[kB];
@@ -103,15 +108,16 @@ __device__ __forceinline__ void mads_step(const FinBest& fb, double bo, int64_t 
         for (int j = 0; j < kB; ++j) {
             const int v = v0 + j * kWave;
             xv[j] = v < n ? x[v] : 0.0;
-            rv[j] = better && v < n ? fb.rp[v] : 0;
+            rv[j] = better && v < np ? fb.rp[v] : 0;
         }
 #pragma unroll
         for (int j = 0; j < kB; ++j) {
             const int v = v0 + j * kWave;
             if (v >= n) break;
-            if (better) {
-                const double d = ltmads_entry(fb.state, n, b, rv[j], c);
-                xn[v] = plus ? xv[j] + d : xv[j] - d;
+            if (better) {   // (a held variable, v >= np: x's double as it is, by a select)
+                const double d = ltmads_entry(fb.state, np, b, rv[j], c);
+                const double moved = plus ? xv[j] + d : xv[j] - d;
+                xn[v] = v < np ? moved : xv[j];
             } else {
                 xn[v] = xv[j];
             }
@@ -141,7 +147,7 @@ __device__ __forceinline__ void argmin_take(double& v1, int& i1, double v2, int 
 // loads every minimum with sc1 loads, in the same wave. The lexicographic (objective, index)
 // minimum is order-independent (the sequential first-best order); NaN / +inf never selected.
 // C: lanes holding the block's candidates (a power of two <= 64). Returns true in the last block.
-template <int C = kFinC>
+template <int C = kFinC, bool kXY = false>
 __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int k, bool have)
 {
     static_assert(C >= 1 && C <= kWave && (C & (C - 1)) == 0, "C: a power of two up to a wave");
@@ -208,7 +214,7 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
         return true;
     }
     if (fb.st) {
-        mads_step(fb, bo, gidx, ell, fcur);
+        mads_step<kXY>(fb, bo, gidx, ell, fcur);
         if (rej && lane == 0) fb.st->skipped += 1;
     }
     if (lane == 0) {
@@ -243,6 +249,7 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
     return true;
 }
 
+template <bool kXY = false>   // (kXY: the pipelined loop's update of an xy-only poll, mads_step)
 __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
     const double* __restrict__ partial, const int* __restrict__ mode, int n_poll, int n_other,
     int K, int N, const int* __restrict__ map, const double* __restrict__ spart,
@@ -332,7 +339,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
                 if (vp) o = -area + vpk;
                 if (obj_out) obj_out[k] = o;
             }
-            if (fb.best && t < kWave) finalize_argmin(fb, o, k, k < K);
+            if (fb.best && t < kWave) finalize_argmin<kFinC, kXY>(fb, o, k, k < K);
             ts_end(ts);
             return;
         }
@@ -377,7 +384,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
         if (vp) o = -area + vpk;
         if (obj_out) obj_out[k] = o;
     }
-    if (fb.best && t < kWave) finalize_argmin(fb, o, k, k < K);
+    if (fb.best && t < kWave) finalize_argmin<kFinC, kXY>(fb, o, k, k < K);
     ts_end(ts);
 }
 

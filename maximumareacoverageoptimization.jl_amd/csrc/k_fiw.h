@@ -1125,7 +1125,7 @@ struct F2Shared {
     const uint8_t* dead;
 };
 
-template <bool kCounts>
+template <bool kCounts, bool kXY = false>   // (kXY: as finalize_kernel's)
 __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     const unsigned* __restrict__ crow, const double* __restrict__ frow, int ldk, int N, int K,
     double w0, const double* __restrict__ vp, double* __restrict__ area_out, double* __restrict__ obj_out,
@@ -1499,7 +1499,7 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     }
     MAC_F2_STAMP(4);
     if (fb.best && t < kWave) {
-        [[maybe_unused]] const bool last = finalize_argmin<C>(fb, o, k, k < K);   // (+ the hint words)
+        [[maybe_unused]] const bool last = finalize_argmin<C, kXY>(fb, o, k, k < K);   // (+ the hint words)
 #ifdef MAC_DIAG
         if (t == 0 && blockIdx.x < 4096) g_diag_f2[8 * blockIdx.x + 7] = last;
 #endif

@@ -133,7 +133,9 @@ __device__ __forceinline__ float key_of(double v, double b, bool& ok)
 // generator): a packed word (dx, dy, dr) is the fp32 key triple (dx, dy, dr), exact by
 // construction; else keyed here from src.get (the generator's distinct directions drawn once per
 // disk).
-template <bool kKeys, int kPer>
+// kXY: an xy-only generated poll (src.np != 0), selected at compile time: the full poll's
+// instantiation is the code it was.
+template <bool kKeys, int kPer, bool kXY = false>
 __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPer <= 3 ? 8 : 4))) void disk_index_kernel(
     uint64_t* ts, CandSrc src0, int N, int K, Grid g, int dedup, IndexOut o)
 {
@@ -210,9 +212,9 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
             y = c[N + i];
             r = c[2 * N + i];
         } else {
-            x = src.get(k, i, N);
-            y = src.get(k, N + i, N);
-            r = src.get(k, 2 * N + i, N);
+            x = kXY ? src.get(k, i, N) : src.get_full(k, i, N);
+            y = kXY ? src.get(k, N + i, N) : src.get_full(k, N + i, N);
+            r = kXY ? src.get(k, 2 * N + i, N) : src.get_full(k, 2 * N + i, N);
         }
     };
 
@@ -278,7 +280,8 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
         get3(0, bx, by, br);
         load_partials();
         const int n = 3 * N;
-        if (!src.cands && 3 * n <= 2 * kIndexSlots && (src.ltri || src.b <= 16384)) {
+        // (a full poll's: an xy-only poll reads its candidates through src.get)
+        if (!kXY && !src.cands && 3 * n <= 2 * kIndexSlots && (src.ltri || src.b <= 16384)) {
             // the generator: candidates k and k + n are x + d and x - d of the same LTMADS entry
             // d = L[rp[v]][cp[k mod n]] (k_prep.h CandSrc), so disk i's 3 x n entries are drawn
             // once into the table's LDS (integers |d| <= b, as int16) and both signs built from

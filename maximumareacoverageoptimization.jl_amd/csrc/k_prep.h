@@ -127,7 +127,9 @@ struct MadsState {
 // Where candidate coordinates come from: a 3N x K column-major matrix (the batch APIs), or a
 // complete LTMADS poll around an incumbent generated on the fly (the native MADS driver):
 // candidate k < n is x + B[:, k], k >= n is x - B[:, k - n], B = L[rp][:, cp] (variable v of a
-// candidate = x_i for v = i, y_i for v = N + i, r_i for v = 2N + i).
+// candidate = x_i for v = i, y_i for v = N + i, r_i for v = 2N + i). An xy-only poll (MAC_POLL_XY:
+// src/TDM_STATIC_opt.jl:15-44) draws its basis over the n_p = 2N variables x_0.., y_0.. alone: 2 n_p
+// candidates, split at n_p, every candidate's radii the incumbent's doubles as they are.
 struct CandSrc {
     const double* cands;   // matrix source when non-null
     int ldc;
@@ -141,6 +143,7 @@ struct CandSrc {
     int64_t b;             // 2^ell
     int k0;                // generator: candidate k of this source is candidate k0 + k of the poll
                            // (a rank's shard of it)
+    int np;                // generator: polled variables n_p, the first n_p of x (0: all 3N)
     const MadsState* mst;  // generator, pipelined MADS loop: b from the device state (else null)
     // the basis form (mac_poll_basis_f64: a caller-owned poll, DirectSearch's B = L[rp][:, cp] and
     // mesh size delta, src/TDM_STATIC_opt.jl:22-44): L's lower triangle packed by rows (int16,
@@ -162,13 +165,17 @@ struct CandSrc {
         b = (int64_t)1 << e;
         return true;
     }
-    // B's entry (r, c) of a generated poll (n = 3N): the stream's LTMADS draw, or delta * L[r][c]
+    // polled variables of a generated poll over N UAVs
+    __host__ __device__ __forceinline__ int polled(int N) const { return np ? np : 3 * N; }
+    // B's entry (r, c) of a generated poll (n = n_p): the stream's LTMADS draw, or delta * L[r][c]
     __device__ __forceinline__ double entry(int n, int r, int c) const
     {
         if (ltri) return r < c ? 0.0 : delta * (double)ltri[(int64_t)r * (r + 1) / 2 + c];
         return ltmads_entry(state, n, b, r, c);
     }
-    __device__ __forceinline__ double get(int kl, int v, int N) const
+    // a full poll's value (np == 0), for the launches that select the poll kind at compile time
+    // (the disk index: its full-poll instantiation is the code it was)
+    __device__ __forceinline__ double get_full(int kl, int v, int N) const
     {
         if (cands) return cands[(int64_t)kl * ldc + v];
         const int n = 3 * N;
@@ -176,6 +183,20 @@ struct CandSrc {
         const int kk = k < n ? k : k - n;
         const double d = entry(n, rp[v], cp[kk]);
         return k < n ? xinc[v] + d : xinc[v] - d;
+    }
+    __device__ __forceinline__ double get(int kl, int v, int N) const
+    {
+        if (cands) return cands[(int64_t)kl * ldc + v];
+        const int n = polled(N);
+        const int k = kl + k0;
+        const int kk = k < n ? k : k - n;
+        // (selects, no branch: the loads stay independent of the compare and issue together; a held
+        // variable, v >= n under an xy-only poll, reads row 0 and keeps x's double as it is, no + 0.0)
+        const bool held = v >= n;
+        const double xv = xinc[v];
+        const double d = entry(n, rp[held ? 0 : v], cp[kk]);
+        const double moved = k < n ? xv + d : xv - d;
+        return held ? xv : moved;
     }
 };
 
@@ -221,7 +242,7 @@ struct PrepArgs {
     PenArgs pa;
     double penalty;
     double* vp;                // per-candidate penalty (null: no objective)
-    int pair;                  // generated complete polls (K = 2n, n % 4 == 0): workgroup cw takes
+    int pair;                  // generated complete polls (K = 2n, n = n_p, n % 4 == 0): workgroup cw takes
                                // x + B[:, k] and x - B[:, k] for k in [4cw, 4cw + 4) (one draw of
                                // each B entry for both: prep_cand)
     int nchain;                // workgroups
@@ -377,10 +398,10 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
     const int N = a.N, K = a.K;
     const int u = threadIdx.x, lane = u & (kWave - 1), wid = u / kWave;
     const int k0 = cw * PC;
-    const int n3 = 3 * N;
+    const int np = a.src.polled(N);   // (generated polls: the polled variables, 3N or 2N)
     // candidate c of the workgroup: k0 + c, or (pairs) the plus / minus candidates of B's columns
     // [4cw, 4cw + 4): c < 4 -> 4cw + c, c >= 4 -> n + 4cw + c - 4
-    auto cand = [&](int c) { return a.pair ? (c < 4 ? 4 * cw + c : n3 + 4 * cw + c - 4) : k0 + c; };
+    auto cand = [&](int c) { return a.pair ? (c < 4 ? 4 * cw + c : np + 4 * cw + c - 4) : k0 + c; };
     const bool obj = a.vp != nullptr;
     const PenArgs& pa = a.pa;
     MAC_PREP_STAMP(0);
@@ -413,7 +434,11 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     const int vv = q * N + ii;
-                    const double d = a.src.entry(n3, a.src.rp[vv], a.src.cp[col]);
+                    if (q == 2 && 2 * N >= np) {   // (uniform) an xy-only poll: the radius as it is, no draw
+                        v[c][q] = v[c + 4][q] = a.src.xinc[vv];
+                        continue;
+                    }
+                    const double d = a.src.entry(np, a.src.rp[vv], a.src.cp[col]);
                     v[c][q] = a.src.xinc[vv] + d;
                     v[c + 4][q] = a.src.xinc[vv] - d;
                 }
@@ -466,7 +491,8 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
                     const double bb = (double)a.src.b;
                     rej = diag_rejects(a.src.xinc[ii], bb, x1, 0, pa.tan_half_fov, T3) &&
                           diag_rejects(a.src.xinc[N + ii], bb, y1, 1, pa.tan_half_fov, T3) &&
-                          diag_rejects(a.src.xinc[2 * N + ii], bb, pa.prev[2 * N + ii], 2, pa.tan_half_fov, T3);
+                          (2 * N >= np ||   // (uniform: over the polled variables only)
+                           diag_rejects(a.src.xinc[2 * N + ii], bb, pa.prev[2 * N + ii], 2, pa.tan_half_fov, T3));
                 }
                 const uint64_t keep = __ballot(!rej);
                 if (lane == 0) wrej[wid] = keep == 0;

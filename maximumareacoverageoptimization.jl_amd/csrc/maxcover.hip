@@ -748,12 +748,15 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
     const int64_t units = (int64_t)K * G;
     // generated complete polls (the native MADS loop: K = 2n): the prep draws each B entry once
     // for its plus and minus candidates (k_prep.h PrepArgs.pair)
-    const bool pair = !src.cands && src.k0 == 0 && K == 6 * N && (3 * N) % 4 == 0 && kPrepC == 8;
+    // (n = the polled variables: 3N, or 2N for an xy-only poll)
+    const int npoll = src.polled(N);
+    const bool pair = !src.cands && src.k0 == 0 && K == 2 * npoll && npoll % 4 == 0 && kPrepC == 8;
     // ... or, with one block of UAVs, prep_x_kernel's layout (k_prep.h prep_block_x<true>): a column
     // triple of B per workgroup (its plus and minus candidates: 6), N workgroups, a ninth wave
     // folding the penalty chains beside the keys and the records
-    const bool gen_x = !src.cands && src.k0 == 0 && K == 6 * N && N >= 1 && N <= kPrepU;
-    const int nchain = pair ? (3 * N) / 4 : (K + kPrepC - 1) / kPrepC;
+    // (full polls only: an xy-only poll takes prep_kernel)
+    const bool gen_x = !src.cands && !src.np && src.k0 == 0 && K == 6 * N && N >= 1 && N <= kPrepU;
+    const int nchain = pair ? npoll / 4 : (K + kPrepC - 1) / kPrepC;
 
     // The fused chain (k_fiw.h: prep -> fiw -> fin2) whenever the poll walk runs on packed keys of at
     // most kFwMaxK + 1 candidates, unless one of the context's last 64 polls did not suit it: a crowded
@@ -885,7 +888,13 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                 fb.feas = d_mirror ? d_feas : nullptr;
             }
             uint64_t* tsf = take_ts(nfin, ts_f, ts_nf);
-            if (counts)
+            if (fb.np && counts)   // (the pipelined loop's update of an xy-only poll)
+                hipLaunchKernelGGL((fin2_kernel<true, true>), dim3(nfin), dim3(kF2Threads), 0, s, L->frows.as<unsigned>(),
+                                   nullptr, ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
+            else if (fb.np)
+                hipLaunchKernelGGL((fin2_kernel<false, true>), dim3(nfin), dim3(kF2Threads), 0, s, nullptr,
+                                   L->frows.as<double>(), ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
+            else if (counts)
                 hipLaunchKernelGGL(fin2_kernel<true>, dim3(nfin), dim3(kF2Threads), 0, s, L->frows.as<unsigned>(),
                                    nullptr, ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
             else
@@ -1021,7 +1030,20 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             const unsigned nidx = 8 * ((N + 7) / 8);
             const int dedup = iper ? 1 : 0;
             uint64_t* tsi = ts_c >= 0 ? take_ts(nidx, ts_i, ts_ni) : nullptr;
-            if (isrc.keysT && iper == kIdxPerWide)
+            // (an xy-only poll's kernels are their own instantiations: the full poll's stay as they were)
+            if (isrc.np && isrc.keysT && iper == kIdxPerWide)
+                hipLaunchKernelGGL((disk_index_kernel<true, kIdxPerWide, true>), dim3(nidx), dim3(kIdxThreads),
+                                   0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
+            else if (isrc.np && isrc.keysT)
+                hipLaunchKernelGGL((disk_index_kernel<true, kIdxPer, true>), dim3(nidx), dim3(kIdxThreads), 0, s,
+                                   tsi, isrc, N, K, ctx->grid, dedup, io);
+            else if (isrc.np && iper == kIdxPerWide)
+                hipLaunchKernelGGL((disk_index_kernel<false, kIdxPerWide, true>), dim3(nidx), dim3(kIdxThreads),
+                                   0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
+            else if (isrc.np)
+                hipLaunchKernelGGL((disk_index_kernel<false, kIdxPer, true>), dim3(nidx), dim3(kIdxThreads), 0,
+                                   s, tsi, isrc, N, K, ctx->grid, dedup, io);
+            else if (isrc.keysT && iper == kIdxPerWide)
                 hipLaunchKernelGGL((disk_index_kernel<true, kIdxPerWide>), dim3(nidx), dim3(kIdxThreads),
                                    0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
             else if (isrc.keysT)
@@ -1202,7 +1224,9 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
         fb.feas = d_mirror ? d_feas : nullptr;
     }
     uint64_t* tsf = ts_c >= 0 ? take_ts(nfin, ts_f, ts_nf) : nullptr;
-    hipLaunchKernelGGL(finalize_kernel, dim3(nfin), dim3(kFinThreads), 0, s,
+    // (fb.np: the pipelined loop's update of an xy-only poll)
+    const auto fin_kern = fb.np ? finalize_kernel<true> : finalize_kernel<false>;
+    hipLaunchKernelGGL(fin_kern, dim3(nfin), dim3(kFinThreads), 0, s,
                        L->partial.as<double>(), d_mode, n_poll, n_other, K, N, d_umap, d_spart, d_ncount,
                        counts, ctx->w0, d_vp, d_area, d_obj, fb, tsf);
     HCK(hipGetLastError());
@@ -2444,6 +2468,8 @@ struct mac_mads {
     Lane* L = nullptr;
     hipStream_t s = nullptr;
     int N = 0, n = 0, K = 0;
+    int np = 0;                   // polled variables (the basis's size): n, or 2N under MAC_POLL_XY; K = 2 np
+    bool xy = false;              // MAC_POLL_XY: x[np..n), the radii, stay as they are
     int64_t lo = 0, hi = 0;
     mac_mads_params prm{};
     double penalty = 1e5, tan_half_fov = 1.0;
@@ -2542,7 +2568,7 @@ static bool poll_rejected(const mac_mads* m, int64_t b)
     if (!m->d_prev) return false;
     const int N = m->N;
     const std::vector<double>& T3 = m->L->h_dlim;
-    for (int v = 0; v < m->n; ++v) {
+    for (int v = 0; v < m->np; ++v) {   // (the polled variables)
         const int q = v / N, i = v % N;
         if (!diag_rejects(m->x[v], (double)b, m->h_prev[v], q, m->tan_half_fov, T3[i])) return false;
     }
@@ -2618,10 +2644,59 @@ int32_t mac_mads_begin(mac_ctx* ctx, const double* x0, int64_t three_n, const do
                                shard_hi, out, nullptr);
 }
 
+// The opts of mac_mads_run_opts / mac_mads_begin_opts: MAC_E_INVAL on an unknown poll kind or a
+// non-zero reserved word; *xy = the xy-only poll (null opts: the full poll).
+static int32_t mads_opts_check(const mac_mads_opts* opts, bool* xy)
+{
+    *xy = false;
+    if (!opts) return MAC_OK;
+    if (opts->poll_vars != MAC_POLL_XYR && opts->poll_vars != MAC_POLL_XY)
+        return fail(MAC_E_INVAL, "mac_mads_opts: unknown poll_vars " + std::to_string(opts->poll_vars));
+    for (int q = 0; q < 3; ++q)
+        if (opts->reserved[q] != 0) return fail(MAC_E_INVAL, "mac_mads_opts: reserved must be 0");
+    *xy = opts->poll_vars == MAC_POLL_XY;
+    return MAC_OK;
+}
+
+static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                               double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                               const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
+                               mac_mads** out, const mac_cons* cons, bool xy);
+
 int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                             const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
                             mac_mads** out, const mac_cons* cons)
+{
+    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
+                           shard_hi, out, cons, false);
+}
+
+int32_t mac_mads_begin_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
+                            mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts)
+{
+    ABI_BEGIN
+    if (!out) return fail(MAC_E_INVAL, "null out");
+    *out = nullptr;
+    bool xy = false;
+    const int32_t rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    if (!xy)   // the full poll: the calls as they are
+        return cons ? mac_mads_begin_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
+                                          shard_lo, shard_hi, out, cons)
+                    : mac_mads_begin(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
+                                     shard_lo, shard_hi, out);
+    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
+                           shard_hi, out, cons, true);
+    ABI_END
+}
+
+static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                               double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                               const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
+                               mac_mads** out, const mac_cons* cons, bool xy)
 {
     ABI_BEGIN
     if (!out) return fail(MAC_E_INVAL, "null out");
@@ -2634,7 +2709,8 @@ int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, con
         return fail(MAC_E_INVAL, "need 0 <= ell0 <= ell_max <= 52");
     const int N = (int)(three_n / 3);
     if (N == 0) return fail(MAC_E_INVAL, "no UAV");
-    const int n = (int)three_n, K = 2 * n;
+    // np: the polled variables (the basis's size), every poll's candidates K = 2 np
+    const int n = (int)three_n, np = xy ? 2 * N : n, K = 2 * np;
     if (shard_lo < 0 || shard_hi > K || shard_lo > shard_hi)
         return fail(MAC_E_INVAL, "shard outside [0, 2n)");
     ConsArgs ca{};
@@ -2655,6 +2731,8 @@ int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, con
         hipStream_t s = m->s;
         m->N = N;
         m->n = n;
+        m->np = np;
+        m->xy = xy;
         m->K = K;
         m->lo = shard_lo;
         m->hi = shard_hi;
@@ -2712,12 +2790,12 @@ int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, con
         // steps over a run; crowding is a property of the UAVs' layout)
         m->route_five = host_crowded_disks(x0, N, std::ldexp(1.0, prm->ell0), ctx->grid.S) > kBitsMinDisks ? 1 : 0;
         m->state = prm->seed;
-        m->T = (uint64_t)n * (uint64_t)(n - 1) / 2;
-        m->per_iter = (uint64_t)n + m->T + 2 * (uint64_t)n;   // ltmads_basis's draws
+        m->T = (uint64_t)np * (uint64_t)(np - 1) / 2;
+        m->per_iter = (uint64_t)np + m->T + 2 * (uint64_t)np;   // ltmads_basis(n_p)'s draws
         // the permutations do not depend on the poll outcomes: the next iteration's are
         // computed on the host while the device evaluates the current poll
-        stream_permutation(m->state, (uint64_t)n + m->T + 1, n, m->rp_next);
-        stream_permutation(m->state, (uint64_t)n + m->T + n + 1, n, m->cp_next);
+        stream_permutation(m->state, (uint64_t)np + m->T + 1, np, m->rp_next);
+        stream_permutation(m->state, (uint64_t)np + m->T + np + 1, np, m->cp_next);
     } catch (...) {
         mads_free(m);
         throw;
@@ -2741,7 +2819,7 @@ int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* bes
     using clk = std::chrono::steady_clock;
     const auto ta = clk::now();
     ++m->it;
-    const int n = m->n;
+    const int n = m->n, np = m->np;
     const int64_t b = (int64_t)1 << m->ell;
     m->rp.swap(m->rp_next);
     m->cp.swap(m->cp_next);
@@ -2759,18 +2837,19 @@ int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* bes
     }
     if (Kc > 0 && !rejected) {
         // (the staging is free: the previous iteration's copies completed at its sync)
-        // one copy of the contiguous staging [incumbent 8n][permutations 4*2n] (n = 3N); the
+        // one copy of the contiguous staging [incumbent 8n][permutations 4*2np] (n = 3N); the
         // staging is free: the previous poll's copy preceded its finalize, whose results were read
         std::copy(m->rp.begin(), m->rp.end(), m->hperm);
-        std::copy(m->cp.begin(), m->cp.end(), m->hperm + n);
+        std::copy(m->cp.begin(), m->cp.end(), m->hperm + np);
         std::copy(m->x.begin(), m->x.end(), m->hx);
-        m->L->xinc.reserve(sizeof(double) * n + sizeof(int) * 2 * n);
-        HCK(hipMemcpyAsync(m->L->xinc.p, m->hx, sizeof(double) * n + sizeof(int) * 2 * n,
+        m->L->xinc.reserve(sizeof(double) * n + sizeof(int) * 2 * np);
+        HCK(hipMemcpyAsync(m->L->xinc.p, m->hx, sizeof(double) * n + sizeof(int) * 2 * np,
                            hipMemcpyHostToDevice, m->s));
         CandSrc src{};
         src.xinc = m->L->xinc.as<double>();
         src.rp = reinterpret_cast<int*>(m->L->xinc.as<double>() + n);
-        src.cp = src.rp + n;
+        src.cp = src.rp + np;
+        src.np = m->xy ? np : 0;
         src.state = m->state;
         src.b = b;
         src.k0 = (int)m->lo;
@@ -2780,8 +2859,8 @@ int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* bes
     const auto tb = clk::now();
     if (m->it < m->prm.n_iter) {
         const uint64_t ns = m->state + m->per_iter * 0x9E3779B97F4A7C15ull;
-        stream_permutation(ns, (uint64_t)n + m->T + 1, n, m->rp_next);
-        stream_permutation(ns, (uint64_t)n + m->T + n + 1, n, m->cp_next);
+        stream_permutation(ns, (uint64_t)np + m->T + 1, np, m->rp_next);
+        stream_permutation(ns, (uint64_t)np + m->T + np + 1, np, m->cp_next);
     }
     const auto tc = clk::now();
     if (Kc > 0 && !rejected) {
@@ -2806,7 +2885,7 @@ int32_t mac_mads_update(mac_mads* m, double best_obj, int64_t best_idx)
     if (!m->polled_b) return fail(MAC_E_INVAL, "mac_mads_update without a poll");
     if (best_idx >= m->K) return fail(MAC_E_INVAL, "best index outside the poll");
     const auto te0 = std::chrono::steady_clock::now();
-    const int n = m->n;
+    const int n = m->np;   // (the polled variables: the rest of x stays as it is)
     const int64_t b = m->polled_b;
     m->polled_b = 0;
     m->evals += m->K;
@@ -2850,7 +2929,7 @@ int32_t mac_mads_poll_ahead(mac_mads* m, int32_t ahead, int32_t* done, double* b
         return MAC_OK;
     }
     set_device(m->ctx);
-    const int n = m->n;
+    const int n = m->n, np = m->np;
     const int ell = m->ell - ahead;
     const int64_t b = (int64_t)1 << ell;
     const uint64_t state = m->state + (uint64_t)ahead * m->per_iter * 0x9E3779B97F4A7C15ull;
@@ -2859,22 +2938,23 @@ int32_t mac_mads_poll_ahead(mac_mads* m, int32_t ahead, int32_t* done, double* b
     if (poll_rejected(m, b)) return MAC_OK;   // (counted by mac_mads_advance once applied)
     if (ahead == 0) {   // the current iteration's permutations are computed already
         std::copy(m->rp_next.begin(), m->rp_next.end(), m->hperm);
-        std::copy(m->cp_next.begin(), m->cp_next.end(), m->hperm + n);
+        std::copy(m->cp_next.begin(), m->cp_next.end(), m->hperm + np);
     } else {
         std::vector<int> rp, cp;
-        stream_permutation(state, (uint64_t)n + m->T + 1, n, rp);
-        stream_permutation(state, (uint64_t)n + m->T + n + 1, n, cp);
+        stream_permutation(state, (uint64_t)np + m->T + 1, np, rp);
+        stream_permutation(state, (uint64_t)np + m->T + np + 1, np, cp);
         std::copy(rp.begin(), rp.end(), m->hperm);
-        std::copy(cp.begin(), cp.end(), m->hperm + n);
+        std::copy(cp.begin(), cp.end(), m->hperm + np);
     }
     std::copy(m->x.begin(), m->x.end(), m->hx);
-    m->L->xinc.reserve(sizeof(double) * n + sizeof(int) * 2 * n);
-    HCK(hipMemcpyAsync(m->L->xinc.p, m->hx, sizeof(double) * n + sizeof(int) * 2 * n,
+    m->L->xinc.reserve(sizeof(double) * n + sizeof(int) * 2 * np);
+    HCK(hipMemcpyAsync(m->L->xinc.p, m->hx, sizeof(double) * n + sizeof(int) * 2 * np,
                        hipMemcpyHostToDevice, m->s));
     CandSrc src{};
     src.xinc = m->L->xinc.as<double>();
     src.rp = reinterpret_cast<int*>(m->L->xinc.as<double>() + n);
-    src.cp = src.rp + n;
+    src.cp = src.rp + np;
+    src.np = m->xy ? np : 0;
     src.state = state;
     src.b = b;
     src.k0 = (int)m->lo;
@@ -2895,7 +2975,7 @@ int32_t mac_mads_advance(mac_mads* m, double best_obj, int64_t best_idx, int32_t
     if (m->polled_b) return fail(MAC_E_INVAL, "mac_mads_advance with a mac_mads_poll pending (use mac_mads_update)");
     if (best_idx >= m->K) return fail(MAC_E_INVAL, "best index outside the poll");
     if (m->it >= m->prm.n_iter || m->ell < 0) return fail(MAC_E_INVAL, "mac_mads_advance past the loop's end");
-    const int n = m->n;
+    const int n = m->np;   // (the polled variables: the rest of x stays as it is)
     const int64_t b = (int64_t)1 << m->ell;
     // the applied poll's whole-poll rejection, decided as mac_mads_poll does (the speculating ranks'
     // own polls ahead are not counted: they may never be applied)
@@ -3001,9 +3081,9 @@ static bool mads_pipelinable(const mac_mads* m)
 static void mads_run_pipelined(mac_mads* m)
 {
     using clk = std::chrono::steady_clock;
-    const int n = m->n;
+    const int n = m->n, np = m->np;
     const int64_t n_iter = m->prm.n_iter;
-    const size_t slot_ints = 2 * (size_t)n;
+    const size_t slot_ints = 2 * (size_t)np;   // a permutation slot: rp, cp of the polled variables
     hipStream_t s = m->s;
     mads_make_slot(m);
     m->d_x.reserve(sizeof(double) * 2 * n);
@@ -3019,10 +3099,10 @@ static void mads_run_pipelined(mac_mads* m)
     auto state_of = [&](int64_t t) { return seed_state + (uint64_t)(t - 1) * step; };
     auto perms_of = [&](int64_t t) {   // into the pinned ring
         int* h = hring + (size_t)((t - 1) % kMadsRing) * slot_ints;
-        stream_permutation(state_of(t), (uint64_t)n + m->T + 1, n, m->rp_next);
-        stream_permutation(state_of(t), (uint64_t)n + m->T + n + 1, n, m->cp_next);
-        std::memcpy(h, m->rp_next.data(), sizeof(int) * n);
-        std::memcpy(h + n, m->cp_next.data(), sizeof(int) * n);
+        stream_permutation(state_of(t), (uint64_t)np + m->T + 1, np, m->rp_next);
+        stream_permutation(state_of(t), (uint64_t)np + m->T + np + 1, np, m->cp_next);
+        std::memcpy(h, m->rp_next.data(), sizeof(int) * np);
+        std::memcpy(h + np, m->cp_next.data(), sizeof(int) * np);
     };
     int64_t uploaded = 0;   // iterations [1, uploaded] on the device
     auto upload_to = [&](int64_t t1) {   // [uploaded + 1, t1]: contiguous slots (chunk aligned)
@@ -3065,7 +3145,8 @@ static void mads_run_pipelined(mac_mads* m)
         CandSrc src{};
         src.xinc = dx + (size_t)((t - 1) & 1) * n;
         src.rp = rp;
-        src.cp = rp + n;
+        src.cp = rp + np;
+        src.np = m->xy ? np : 0;
         src.state = state_of(t);
         src.b = 0;   // from the device state
         src.k0 = 0;
@@ -3079,6 +3160,7 @@ static void mads_run_pipelined(mac_mads* m)
         fbm.cp = src.cp;
         fbm.state = src.state;
         fbm.n = n;
+        fbm.np = src.np;
         fbm.ell_max = (int)m->prm.ell_max;
         fbm.done_seq = kMadsDoneSeq;
         enqueue_eval(m->ctx, m->L, s, src, m->N, m->K, true, m->L->rmax.as<double>(), m->penalty,
@@ -3123,15 +3205,49 @@ int32_t mac_mads_run(mac_ctx* ctx, const double* x0, int64_t three_n, const doub
                              nullptr);
 }
 
+static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                             const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
+                             bool xy);
+
 int32_t mac_mads_run_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                           double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                           const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons)
 {
+    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons,
+                         false);
+}
+
+int32_t mac_mads_run_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
+                          const mac_mads_opts* opts)
+{
+    ABI_BEGIN
+    bool xy = false;
+    const int32_t rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    if (!xy)   // the full poll: the calls as they are
+        return cons ? mac_mads_run_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
+                                        x_out, st, cons)
+                    : mac_mads_run(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out,
+                                   st);
+    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons,
+                         true);
+    ABI_END
+}
+
+static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                             const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
+                             bool xy)
+{
     ABI_BEGIN
     if (!x_out) return fail(MAC_E_INVAL, "null argument");
     mac_mads* m = nullptr;
-    int32_t rc = mac_mads_begin_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
-                                     0, 2 * three_n, &m, cons);
+    // the whole poll: every candidate of the 2 n_p (n_p = 3N, or 2N for the xy-only poll)
+    int32_t rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
+                                 xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy);
     if (rc) return rc;
     if (mads_pipelinable(m)) {
         try {
