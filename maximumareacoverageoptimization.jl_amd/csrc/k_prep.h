@@ -198,6 +198,19 @@ struct CandSrc {
         const double moved = k < n ? xv + d : xv - d;
         return held ? xv : moved;
     }
+    // The source selected at compile time (the fused chain's second and third launches, k_fiw.h):
+    // kMat is a matrix source, read from cands alone — no generator code in that instantiation and
+    // none of its operands held in registers — and never paused by a device state (no mst).
+    template <bool kMat> __device__ __forceinline__ double val(int kl, int v, int N) const
+    {
+        if constexpr (kMat) return cands[(int64_t)kl * ldc + v];
+        else return cands ? cands[(int64_t)kl * ldc + v] : get(kl, v, N);
+    }
+    template <bool kMat> __device__ __forceinline__ bool resolve_as()
+    {
+        if constexpr (kMat) return true;
+        else return resolve();
+    }
 };
 
 // ------------------------------------------------------------------ the prep launch

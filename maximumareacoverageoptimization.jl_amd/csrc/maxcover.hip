@@ -865,8 +865,12 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             uint64_t* tsw = take_ts(nfw, ts_w, ts_nw);
             ts_a = ts_w;   // (mac_profile_read: the walk launch)
             ts_na = ts_nw;
-            if (counts) hipLaunchKernelGGL(fiw_kernel<true>, dim3(nfw), dim3(kFwThreads), 0, s, tsw, fa);
-            else hipLaunchKernelGGL(fiw_kernel<false>, dim3(nfw), dim3(kFwThreads), 0, s, tsw, fa);
+            // the source selects the instantiation of both launches (k_fiw.h kMat): a matrix poll's
+            // has no generator code in it; generated and basis-form polls take the other
+            const bool mat = src.cands != nullptr;
+            const auto fiw_kern = counts ? (mat ? fiw_kernel<true, true> : fiw_kernel<true, false>)
+                                         : (mat ? fiw_kernel<false, true> : fiw_kernel<false, false>);
+            hipLaunchKernelGGL(fiw_kern, dim3(nfw), dim3(kFwThreads), 0, s, tsw, fa);
             HCK(hipGetLastError());
             if (ctx->host_stats) h3 = hclk::now();
             const unsigned nfin = 8 * (unsigned)((K + 8 * kF2C - 1) / (8 * kF2C));
@@ -888,18 +892,14 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                 fb.feas = d_mirror ? d_feas : nullptr;
             }
             uint64_t* tsf = take_ts(nfin, ts_f, ts_nf);
-            if (fb.np && counts)   // (the pipelined loop's update of an xy-only poll)
-                hipLaunchKernelGGL((fin2_kernel<true, true>), dim3(nfin), dim3(kF2Threads), 0, s, L->frows.as<unsigned>(),
-                                   nullptr, ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
-            else if (fb.np)
-                hipLaunchKernelGGL((fin2_kernel<false, true>), dim3(nfin), dim3(kF2Threads), 0, s, nullptr,
-                                   L->frows.as<double>(), ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
-            else if (counts)
-                hipLaunchKernelGGL(fin2_kernel<true>, dim3(nfin), dim3(kF2Threads), 0, s, L->frows.as<unsigned>(),
-                                   nullptr, ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
-            else
-                hipLaunchKernelGGL(fin2_kernel<false>, dim3(nfin), dim3(kF2Threads), 0, s, nullptr,
-                                   L->frows.as<double>(), ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
+            // (fb.np: the pipelined loop's update of an xy-only poll, a generated source)
+            const bool xy = fb.np != 0 && !mat;
+            const auto fin2_kern =
+                counts ? (mat ? fin2_kernel<true, true> : xy ? fin2_kernel<true, false, true> : fin2_kernel<true, false>)
+                       : (mat ? fin2_kernel<false, true> : xy ? fin2_kernel<false, false, true> : fin2_kernel<false, false>);
+            hipLaunchKernelGGL(fin2_kern, dim3(nfin), dim3(kF2Threads), 0, s,
+                               counts ? L->frows.as<unsigned>() : nullptr, counts ? nullptr : L->frows.as<double>(),
+                               ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
             HCK(hipGetLastError());
             if (ctx->host_stats) {
                 const auto h4 = hclk::now();
