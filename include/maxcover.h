@@ -252,8 +252,9 @@ typedef struct mac_cons {
  * the spacing with nobody (sqrt(NaN) < d and inf < d are false) and does not disturb the test of the
  * other UAVs; a NaN y or r never satisfies cons7's comparisons. d_sep = +inf rejects every candidate
  * with two UAVs at a finite squared distance. N = 1 has no pairs: always feasible under cons8.
- * cons5 (:106-119, per-UAV target speed) is deliberately not here: it is cons3 with
- * tan_half_fov = 1, prev = the previous target and d_lim = 2, which the poll calls already take.
+ * cons4, cons5 and cons6 (:78-138), which limit how a target moves from one MPC step to the next,
+ * have a descriptor of their own (mac_motion, below): cons5 is cons3's test with tan_half_fov = 1,
+ * but cons3 has one prev / d_lim slot and the reference passes both constraints at once.
  * Caller-owned polls take a mac_cons through the calls below; the native MADS driver (candidates
  * generated on the device) through mac_mads_run_cons / mac_mads_begin_cons.
  *
@@ -281,6 +282,53 @@ int32_t mac_poll_best_cons_f64(mac_ctx* ctx, const double* cands, int64_t three_
                                const double* prev, const double* d_lim, double tan_half_fov,
                                double* obj_out, double* best_obj, int64_t* best_idx,
                                const mac_cons* cons);
+
+/* ---- target-motion constraints on the device (src/TDM_Constraints.jl cons4, cons5, cons6) ---- */
+/* The extreme constraints that limit the move of each UAV's target away from the previous MADS
+ * target, the anchor a = [x; y; R] (the reference's single_output). For UAV i of a candidate c:
+ * t = (c.x_i - a.x_i, c.y_i - a.y_i, c.R_i - a.R_i), q2 = fl(fl(tx*tx) + fl(ty*ty)),
+ * q3 = fl(q2 + fl(tz*tz)); fp64 throughout, ^2 = x*x, no FMA, as cons3. A candidate is infeasible
+ * iff some i has
+ *   cons5 (:106-119)  sqrt(q3) > v_max                        (the reference's 2)
+ *   cons6 (:122-138)  |sqrt(q3) - speed_prev[i]| > a_max      (the reference's 1)
+ *   cons4 (:78-103)   c < cone_cos,  c = fl(fl(fl(ux*tx) + fl(uy*ty)) /
+ *                       fl(fl(sqrt(fl(fl(ux*ux) + fl(uy*uy)))) * fl(sqrt(q2)))),  u = (vx_i, vy_i).
+ *                     The reference's abs(acosd(round(c))) > 90 is exactly c < -0.5 (round is
+ *                     ties-to-even: round(-0.5) = -0 gives 90 degrees, not > 90), so its value is
+ *                     cone_cos = -0.5. A zero velocity or a zero move gives c = NaN: feasible.
+ * cons5 and cons6 are decided on q3 against thresholds built on the host (no square root on the
+ * device; mac_motion_thresholds); cons4 takes one fp64 square root and one division per UAV.
+ * A NaN in any operand follows the arithmetic: every comparison is false and the UAV is feasible.
+ * Not pinned: Julia's norm and dot go through a scaled generic_norm2 and BLAS, which may differ from
+ * this plain form in the last ulp; parity is pinned against the package's host callables
+ * (TDM_Constraints.create_cons4 / 5 / 6), not against Julia. */
+typedef struct mac_motion {
+    const double* anchor;      /* 3N: the previous target [x; y; R]. NULL: everything off          */
+    const double* vel;         /* 2N: [vx; vy], the UAVs' xy velocity (cons4). NULL: cons4 off     */
+    const double* speed_prev;  /* N: the norm of the previous target velocity (cons6). NULL: off   */
+    double cone_cos;           /* cons4. NaN: off                                                  */
+    double v_max;              /* cons5. NaN: off                                                  */
+    double a_max;              /* cons6. NaN: off                                                  */
+} mac_motion;
+/* The three arrays are host pointers, copied at the call (or at mac_mads_begin_motion, for the
+ * stepper's lifetime). Each entry point below is the call named in its comment plus a mac_motion;
+ * motion = NULL or every constraint off forwards to that call before touching anything (the same
+ * launches, bit-identical outputs and statistics). With a constraint on, N <= 2048 (MAC_E_INVAL
+ * above), the mask launch also runs with every mac_cons constraint off (without the sort: a load, the
+ * tests and one flag per workgroup), and a rejected candidate is treated exactly as a mac_cons
+ * rejection is. There are no _dev and no _f32 forms of these calls. */
+/* mac_cons_mask_f64 under a mac_motion. */
+int32_t mac_cons_mask_motion_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                                 const mac_cons* cons, uint8_t* feasible_out, const mac_motion* motion);
+/* mac_poll_best_cons_f64 under a mac_motion. */
+int32_t mac_poll_best_motion_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                                 const double* r_max, double penalty,
+                                 const double* prev, const double* d_lim, double tan_half_fov,
+                                 double* obj_out, double* best_obj, int64_t* best_idx,
+                                 const mac_cons* cons, const mac_motion* motion);
+/* cons6's thresholds for one UAV: |fl(sqrt q3) - speed_prev| > a_max  <=>  q3 > *q_hi || q3 <= *q_lo
+ * for every double q3 >= 0 (+inf / -1: that side never rejects). Host arithmetic only; no context. */
+void mac_motion_thresholds(double speed_prev, double a_max, double* q_hi, double* q_lo);
 
 /* ---- native MADS driver ------------------------------------------ */
 /* A granular MADS with a complete LTMADS poll, the restatement of DirectSearch's Optimize!
@@ -421,6 +469,21 @@ int32_t mac_mads_begin_opts(mac_ctx* ctx, const double* x0, int64_t three_n, con
                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                             const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
                             mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts);
+/* mac_mads_run_opts / mac_mads_begin_opts under a mac_motion (see mac_motion; src/FullSimulation.jl:85,
+ * :96 build cons4 in every MPC step): every poll's mask launch also decides the motion constraints, and
+ * a rejected candidate is treated as a mac_cons rejection is: not evaluated for N <= 512, evaluated
+ * and then +inf above, not counted in feasible_evaluations; f(x0) = +inf when x0 is rejected. Holds
+ * under MAC_POLL_XY (the radii stay, so tz = x0's), for any shard and in mac_mads_poll_ahead; the ranks
+ * of a sharded loop pass the same motion. motion = NULL or all off: the _opts call itself. */
+int32_t mac_mads_run_motion(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* params, double* x_out, mac_mads_stats* stats,
+                            const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion);
+int32_t mac_mads_begin_motion(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                              const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
+                              mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts,
+                              const mac_motion* motion);
 
 /* fp32 candidates (config 3's "fp32" caller path; SURVEY 8(b) "*_f32: coords f32, accum f64"):
  * the candidate matrix (and prev) are uploaded as floats and widened exactly on the device;

@@ -18,7 +18,7 @@ is what the parity tests exercise. See INTEGRATION.md.
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacCons, cons_mask,
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacCons, MacMotion, cons_mask,
        set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
@@ -221,6 +221,37 @@ struct MacCons
 end
 MacCons(; d_sep::Real = NaN, zone_y::Real = NaN, zone_r::Real = NaN) = MacCons(d_sep, zone_y, zone_r)
 
+"""
+MacMotion — the target-motion constraints (mac_motion, include/maxcover.h): cons4 (`cone_cos` with
+`vel` = [vx; vy], src/TDM_Constraints.jl:78-103; -0.5 there), cons5 (`v_max`, :106-119; 2) and cons6
+(`a_max` with `speed_prev`, :122-138; 1) around the previous target `anchor` = [x; y; R]. A NaN scalar
+or `nothing` for its array switches a constraint off. The arrays are copied by each call. Like the
+rest of this shim, never executed here.
+"""
+struct MacMotion
+    anchor::Vector{Float64}
+    vel::Union{Nothing,Vector{Float64}}
+    speed_prev::Union{Nothing,Vector{Float64}}
+    cone_cos::Float64
+    v_max::Float64
+    a_max::Float64
+end
+MacMotion(anchor::Vector{Float64}; vel = nothing, speed_prev = nothing, cone_cos::Real = NaN,
+          v_max::Real = NaN, a_max::Real = NaN) = MacMotion(anchor, vel, speed_prev, cone_cos, v_max, a_max)
+
+# mac_motion's C layout (three host pointers, three doubles); the arrays must be GC.@preserve'd
+struct CMotion
+    anchor::Ptr{Float64}
+    vel::Ptr{Float64}
+    speed_prev::Ptr{Float64}
+    cone_cos::Float64
+    v_max::Float64
+    a_max::Float64
+end
+_ptr_or_null(v) = v === nothing ? Ptr{Float64}(C_NULL) : pointer(v)
+CMotion(m::MacMotion) = CMotion(pointer(m.anchor), _ptr_or_null(m.vel), _ptr_or_null(m.speed_prev),
+                                m.cone_cos, m.v_max, m.a_max)
+
 """Feasibility (Bool per column) of the 3N x K candidates under `cons`; needs no point list."""
 function cons_mask(cands::Matrix{Float64}, cons::MacCons, ctx::MacContext)
     K = size(cands, 2)
@@ -242,15 +273,26 @@ keeps the plain call. Returns (best_obj, best_idx (1-based, 0 if none feasible),
 function poll_best(cands::Matrix{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                    penalty::Float64 = 1e5, prev::Union{Nothing,Vector{Float64}} = nothing,
                    d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
-                   cons::Union{Nothing,MacCons} = nothing)
+                   cons::Union{Nothing,MacCons} = nothing, motion::Union{Nothing,MacMotion} = nothing)
     K = size(cands, 2)
     objs = Vector{Float64}(undef, K)
     bo = Ref{Float64}(Inf)
     bi = Ref{Int64}(-1)
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
-    GC.@preserve prev d_lim begin
-        if cons === nothing
+    GC.@preserve prev d_lim motion begin
+        if motion !== nothing   # mac_poll_best_motion_f64: cons4 / cons5 / cons6 as well
+            rcons = cons === nothing ? nothing : Ref(cons)
+            GC.@preserve rcons begin
+                pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)
+                check(ccall((:mac_poll_best_motion_f64, libmaxcover), Int32,
+                            (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
+                             Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ref{Float64}, Ref{Int64},
+                             Ptr{MacCons}, Ref{CMotion}),
+                            ctx, cands, size(cands, 1), K, r_max, penalty, pprev, pdlim, tan_half_fov,
+                            objs, bo, bi, pcons, Ref(CMotion(motion))))
+            end
+        elseif cons === nothing
             check(ccall((:mac_poll_best_f64, libmaxcover), Int32,
                         (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
                          Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ref{Float64}, Ref{Int64}),
@@ -378,7 +420,8 @@ With `cons::MacCons` (mac_mads_run_cons) every poll also applies cons8 / cons7 o
 evaluated; `nothing` keeps the plain call. `poll_vars = :xy` (mac_mads_run_opts, MAC_POLL_XY) polls
 x and y only — 4N candidates per poll from a basis of size 2N, the radii of `x` equal to `x0`'s bit
 for bit — for the steps where "no height changes need to be explored" (src/TDM_STATIC_opt.jl:15-44);
-`:xyr`, the default, is the calls above. Like the rest of this shim, the `poll_vars` path has not been
+`:xyr`, the default, is the calls above. `motion::MacMotion` (mac_mads_run_motion) adds cons4 / cons5 /
+cons6 to every poll's mask. Like the rest of this shim, the `poll_vars` and `motion` paths have not been
 executed here. Returns (x, stats::MadsStats).
 """
 function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
@@ -386,15 +429,26 @@ function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                   d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
                   n_iter::Integer = 100, ell0::Integer = 2, ell_max::Integer = 6,
                   seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing,
-                  poll_vars::Symbol = :xyr)
+                  poll_vars::Symbol = :xyr, motion::Union{Nothing,MacMotion} = nothing)
     opts = MadsOpts(poll_vars)
     x = similar(x0)
     prm = Ref(MadsParams(n_iter, ell0, ell_max, UInt64(seed)))
     st = Ref{MadsStats}()
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
-    GC.@preserve prev d_lim begin
-        if opts.poll_vars != 0
+    GC.@preserve prev d_lim motion begin
+        if motion !== nothing
+            rcons = cons === nothing ? nothing : Ref(cons)
+            GC.@preserve rcons begin
+                pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)
+                check(ccall((:mac_mads_run_motion, libmaxcover), Int32,
+                            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                             Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats},
+                             Ptr{MacCons}, Ref{MadsOpts}, Ref{CMotion}),
+                            ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st,
+                            pcons, Ref(opts), Ref(CMotion(motion))))
+            end
+        elseif opts.poll_vars != 0
             rcons = cons === nothing ? nothing : Ref(cons)   # (kept alive across the call)
             GC.@preserve rcons begin
                 pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)

@@ -76,16 +76,51 @@ def split_cons_ext(cons_ext):
     mac_cons mapping the native driver takes (TDM_Constraints.merge_mac_cons; None: nothing on).
     ``cons1`` (always true) is dropped. A constraint the device cannot apply — a plain callable, or
     a second constraint of a kind already merged — raises ValueError naming it: the native driver
-    generates its candidates on the device and calls no host function. Needs no GPU."""
-    from .TDM_Constraints import cons1, merge_mac_cons
+    generates its candidates on the device and calls no host function. The target-motion
+    constraints (create_cons4 / create_cons5 / create_cons6) are merged into one mac_motion mapping
+    (merge_mac_motion), returned under the key ``"motion"`` of the result. Needs no GPU."""
+    from .TDM_Constraints import cons1, merge_mac_cons, merge_mac_motion
     if callable(cons_ext):
         cons_ext = [cons_ext]
     merged, plain = merge_mac_cons([c for c in (cons_ext or ()) if c is not cons1])
+    motion, plain = merge_mac_motion(plain)
     if plain:
         names = ", ".join(getattr(c, "__name__", repr(c)) for c in plain)
         raise ValueError(f"cons_ext: {names} cannot run in the native MADS driver (no mac_cons data, "
                          "or a second constraint of a kind already given)")
+    if motion is not None:
+        merged = dict(merged or {}, motion=motion)
     return merged
+
+
+def derive_motion(outputs, params, velocities=None, t=None):
+    """The mac_motion mapping of MPC step ``t`` from the MADS outputs so far (None before two exist:
+    "only activate after one iteration"): anchor = outputs[-1] (the reference's single_output);
+    speed_prev[i] = the 3-D norm of UAV i's last target move outputs[-1] - outputs[-2], in the plain
+    form sqrt(dx*dx + dy*dy + dz*dz); vel = the xy part of that move (perfect tracking), or what
+    ``velocities(t)`` returns ([vx; vy], 2N). ``params``: cone_cos / v_max / a_max (missing or None:
+    that constraint is off). Pure host arithmetic, the same on every rank."""
+    if len(outputs) < 2:
+        return None
+    a = np.ascontiguousarray(np.asarray(outputs[-1], dtype=np.float64))
+    b = np.asarray(outputs[-2], dtype=np.float64)
+    N = a.size // 3
+    d = a - b
+    dx, dy, dz = d[:N], d[N:2 * N], d[2 * N:]
+    m = {"anchor": a}
+    if params.get("cone_cos") is not None:
+        vel = np.concatenate([dx, dy]) if velocities is None else \
+            np.asarray(velocities(t), dtype=np.float64).ravel()
+        if vel.size != 2 * N:
+            raise ValueError("velocities(t) must return 2N values [vx; vy]")
+        m["vel"] = np.ascontiguousarray(vel)
+        m["cone_cos"] = float(params["cone_cos"])
+    if params.get("v_max") is not None:
+        m["v_max"] = float(params["v_max"])
+    if params.get("a_max") is not None:
+        m["speed_prev"] = np.sqrt(dx * dx + dy * dy + dz * dz)
+        m["a_max"] = float(params["a_max"])
+    return m if len(m) > 1 else None
 
 
 class Simulation:
@@ -106,14 +141,19 @@ class Simulation:
     ``poll_vars``: "xyr" (every variable, the default), "xy" (x and y only, the radii held:
     MAC_POLL_XY, the reference's CustomPoll, src/TDM_STATIC_opt.jl:15-44) or "auto" (per step, on the
     host after the r_max rule: auto_poll_vars); under "xy" and "auto" each record gains ``poll_vars``,
-    what the step used (the default's records keep the keys they had)."""
+    what the step used (the default's records keep the keys they had).
+    ``motion``: ``dict(cone_cos=, v_max=, a_max=)`` (the reference's -0.5, 2 and 1; a missing key: off)
+    switches on cons4 / cons5 / cons6 (include/maxcover.h mac_motion) from t >= 3 on, around the
+    previous MADS output (derive_motion); ``velocities``: a callable t -> [vx; vy] for cons4, None:
+    the last target move (perfect tracking). Every rank derives the same arrays in all three modes;
+    with ``motion=None`` the records and calls are what they were."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
                  shard=None, gather=None, speculate: bool | None = None, device=None,
                  attribution: bool = False, cons_ext=(), high_interest=None, w_high=None,
-                 poll_vars: str = "xyr"):
+                 poll_vars: str = "xyr", motion=None, velocities=None):
         if poll_vars not in ("xyr", "xy", "auto"):
             raise ValueError(f"poll_vars must be 'xyr', 'xy' or 'auto', not {poll_vars!r}")
         self.poll_vars = poll_vars
@@ -122,6 +162,15 @@ class Simulation:
         if self.high_interest is None and w_high is not None:
             raise ValueError("w_high needs high_interest")
         self.cons = split_cons_ext(cons_ext)
+        # motion constraints given as cons_ext callables keep their own (fixed) anchor
+        self.cons_motion = self.cons.pop("motion", None) if self.cons else None
+        self.cons = self.cons or None
+        if motion is not None and self.cons_motion is not None:
+            raise ValueError("motion= and a motion constraint in cons_ext share the one mac_motion")
+        if motion is not None and set(motion) - {"cone_cos", "v_max", "a_max"}:
+            raise ValueError("motion: the keys are cone_cos, v_max and a_max")
+        self.motion = dict(motion) if motion is not None else None
+        self.velocities = velocities
         # per-UAV attribution of each step's MADS output (one mac_area_by_disk_f64 call per step)
         self.attribution = bool(attribution)
         self.x_prev = np.asarray(starting_circles, dtype=np.float64).copy()
@@ -218,6 +267,11 @@ class Simulation:
                   ell0=self.ell0, ell_max=self.ell_max, seed=self.seed + t)
         if self.cons is not None:
             kw["cons"] = self.cons
+        mo = self.cons_motion
+        if self.motion is not None and t >= 3:
+            mo = derive_motion(self.outputs, self.motion, self.velocities, t)
+        if mo is not None:
+            kw["motion"] = mo
         pvars = self.poll_vars
         if pvars == "auto":
             pvars = auto_poll_vars(single_input[2 * N:], self.r_max)

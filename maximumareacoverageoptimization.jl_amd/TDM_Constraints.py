@@ -6,7 +6,11 @@ test inside libmaxcover (finalize kernel, exact threshold form).
 
 ``create_cons8`` (:157-172, minimum spacing) and ``create_cons7`` (:142-154, altitude zone) are the
 swarm constraints written for the reference's ``cons_ext`` slot; they carry ``mac_cons`` fields, which
-``TDM_STATIC_opt.mads`` merges into one descriptor for the device (include/maxcover.h mac_cons)."""
+``TDM_STATIC_opt.mads`` merges into one descriptor for the device (include/maxcover.h mac_cons).
+
+``create_cons4`` (:78-103, velocity cone), ``create_cons5`` (:106-119, target speed) and
+``create_cons6`` (:122-138, target acceleration) limit the move away from the previous target; they
+carry ``mac_motion`` fields, merged the same way (include/maxcover.h mac_motion)."""
 from __future__ import annotations
 
 import math
@@ -88,6 +92,120 @@ def create_cons8(d_sep: float = 15.0):
 
     cons8.mac_cons = {"d_sep": d}
     return cons8
+
+
+def _anchor(anchor) -> np.ndarray:
+    """[x; y; R] (3N doubles) from a list of Circle or the vector itself."""
+    from .AreaCoverageCalculation import make_MADS
+    a = anchor
+    if len(a) and not isinstance(a[0], (float, int, np.floating, np.integer)):
+        a = make_MADS(a)
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())
+
+
+def _move(xx, a, N: int, i: int):
+    """UAV i's move t = x - a and q2 = fl(fl(tx*tx) + fl(ty*ty)) (Python floats: IEEE, no FMA)."""
+    tx = float(xx[i]) - float(a[i])
+    ty = float(xx[N + i]) - float(a[N + i])
+    tz = float(xx[2 * N + i]) - float(a[2 * N + i])
+    return tx, ty, tz, tx * tx + ty * ty
+
+
+def _sqrt(q: float) -> float:
+    return math.sqrt(q) if q >= 0.0 and q != math.inf else float(np.sqrt(np.float64(q)))
+
+
+def cone_cosine(ux: float, uy: float, tx: float, ty: float) -> float:
+    """cons4's c = dot(u, t) / (|u| |t|) in the device's plain form (include/maxcover.h mac_motion);
+    0/0 (a zero velocity or a zero move) and inf/inf give NaN, as IEEE division does."""
+    q2 = tx * tx + ty * ty
+    with np.errstate(all="ignore"):
+        den = np.float64(_sqrt(ux * ux + uy * uy)) * np.float64(_sqrt(q2))
+        return float(np.float64(ux * tx + uy * ty) / den)
+
+
+def create_cons4(velocities, anchor, cone_cos: float = -0.5):
+    """src/TDM_Constraints.jl:78-103 (the target stays inside a cone around the UAV's xy velocity,
+    "to reduce oscillatory target setting"). ``velocities``: [vx; vy] (2N values);
+    ``anchor``: the previous MADS target, [x; y; R] or Circles. The reference's
+    ``abs(acosd(round(c))) > 90`` is ``c < -0.5`` (round is ties-to-even), hence the default.
+    Carries ``mac_motion`` (anchor, vel, cone_cos) for the device."""
+    a = _anchor(anchor)
+    N = a.size // 3
+    v = np.ascontiguousarray(np.asarray(velocities, dtype=np.float64).ravel())
+    if v.size != 2 * N:
+        raise ValueError("velocities: 2N values [vx; vy]")
+    cc = float(cone_cos)
+
+    def cons4(x) -> bool:
+        xx = np.asarray(x, dtype=np.float64)
+        for i in range(N):
+            tx, ty, _, _ = _move(xx, a, N, i)
+            if cone_cosine(float(v[i]), float(v[N + i]), tx, ty) < cc:
+                return False
+        return True
+
+    cons4.mac_motion = {"anchor": a, "vel": v, "cone_cos": cc}
+    return cons4
+
+
+def create_cons5(anchor, v_max: float = 2.0):
+    """src/TDM_Constraints.jl:106-119 (target speed): infeasible when some UAV's 3-D move from
+    ``anchor`` is longer than ``v_max`` (2 in the reference). Carries ``mac_motion``."""
+    a = _anchor(anchor)
+    N = a.size // 3
+    vm = float(v_max)
+
+    def cons5(x) -> bool:
+        xx = np.asarray(x, dtype=np.float64)
+        for i in range(N):
+            _, _, tz, q2 = _move(xx, a, N, i)
+            if _sqrt(q2 + tz * tz) > vm:
+                return False
+        return True
+
+    cons5.mac_motion = {"anchor": a, "v_max": vm}
+    return cons5
+
+
+def create_cons6(anchor, speed_prev, a_max: float = 1.0):
+    """src/TDM_Constraints.jl:122-138 (target acceleration): infeasible when some UAV's speed
+    |x - anchor| differs from ``speed_prev[i]`` (the norm of its previous target velocity) by more
+    than ``a_max`` (1 in the reference). Carries ``mac_motion``."""
+    a = _anchor(anchor)
+    N = a.size // 3
+    sp = np.ascontiguousarray(np.asarray(speed_prev, dtype=np.float64).ravel())
+    if sp.size != N:
+        raise ValueError("speed_prev: N values")
+    am = float(a_max)
+
+    def cons6(x) -> bool:
+        xx = np.asarray(x, dtype=np.float64)
+        for i in range(N):
+            _, _, tz, q2 = _move(xx, a, N, i)
+            if abs(_sqrt(q2 + tz * tz) - float(sp[i])) > am:
+                return False
+        return True
+
+    cons6.mac_motion = {"anchor": a, "speed_prev": sp, "a_max": am}
+    return cons6
+
+
+def merge_mac_motion(constraints):
+    """One mac_motion dict {anchor, vel, speed_prev, cone_cos, v_max, a_max} out of the callables
+    that carry ``mac_motion`` data (None when there is none), and the list of the callables that do
+    not. The descriptor has one anchor and one slot per kind: a constraint of a kind already taken,
+    or around another anchor, stays a host callable."""
+    merged, plain = {}, []
+    for c in constraints:
+        data = getattr(c, "mac_motion", None)
+        if data and not ((set(data) - {"anchor"}) & set(merged)) and \
+                ("anchor" not in merged or np.array_equal(merged["anchor"], data["anchor"],
+                                                          equal_nan=True)):
+            merged.update(data)
+        else:
+            plain.append(c)
+    return (merged or None), plain
 
 
 def merge_mac_cons(constraints):

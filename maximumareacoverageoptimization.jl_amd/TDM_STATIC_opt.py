@@ -18,7 +18,7 @@ import time
 import numpy as np
 
 from ._lib import Context, InexactError, default_context
-from .TDM_Constraints import merge_mac_cons
+from .TDM_Constraints import merge_mac_cons, merge_mac_motion
 from .workloads import SplitMix64, ltmads_basis
 
 PENALTY = 1e5  # :97
@@ -51,15 +51,18 @@ def createObjective(cells, N: int, r_max, ctx: Context | None = None):
             raise ValueError("batch expects K x 3N")
         return ctx.objective_batch(Xa, np.asarray(r_max, dtype=np.float64), PENALTY)
 
-    def poll(X, cons3=None, cons=None):
-        """(best_obj, best_idx, objectives) with cons3 and the swarm constraints ``cons`` (a mac_cons
-        mapping, TDM_Constraints.merge_mac_cons) applied on the device."""
+    def poll(X, cons3=None, cons=None, motion=None):
+        """(best_obj, best_idx, objectives) with cons3, the swarm constraints ``cons`` (a mac_cons
+        mapping, TDM_Constraints.merge_mac_cons) and the target-motion constraints ``motion`` (a
+        mac_motion mapping, merge_mac_motion) applied on the device."""
         Xa = np.asarray(X, dtype=np.float64)
         kw = {}
         if cons3 is not None and hasattr(cons3, "prev"):
             kw = dict(prev=cons3.prev, d_lim=cons3.d_lim, tan_half_fov=cons3.tan_half_fov)
         if cons is not None:
             kw["cons"] = cons
+        if motion is not None:
+            kw["motion"] = motion
         return ctx.poll_best(Xa, np.asarray(r_max, dtype=np.float64), PENALTY, want_all=True,
                              **kw)
 
@@ -124,7 +127,8 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
     ell_max) (larger steps); failure: ell <- ell-1; stop when ell < 0 (below the granularity
     1.0 of every variable, src/TDM_STATIC_opt.jl:131-137) or after N_iter iterations (:126).
     With a batched objective (``obj.poll``), cons3 and the constraints carrying ``mac_cons`` data
-    (TDM_Constraints.create_cons8 / create_cons7) are applied on the device inside the poll; the
+    (TDM_Constraints.create_cons8 / create_cons7) or ``mac_motion`` data (create_cons4 / create_cons5 /
+    create_cons6) are applied on the device inside the poll; the
     iterates are the ones the same constraints give as plain host callables.
     ``poll_vars="xy"``: the basis is drawn over the n_p = 2N variables x, y (same stream, n := n_p)
     and the radii are held (MAC_POLL_XY, include/maxcover.h)."""
@@ -142,9 +146,10 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
     others = [c for c in cons if c is not cons3]
     # the swarm constraints that carry device data (create_cons8 / create_cons7) go to the poll as
     # one mac_cons; only the remaining plain callables are evaluated per candidate on the host
-    dev_cons = None
+    dev_cons = dev_motion = None
     if hasattr(obj, "poll"):
         dev_cons, others = merge_mac_cons(others)
+        dev_motion, others = merge_mac_motion(others)   # (cons4 / cons5 / cons6: one mac_motion)
     f = obj(x) if feasible(x) else np.inf
     res.status.function_evaluations += 1
     ell = ell0
@@ -162,7 +167,10 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
                 bo, bi = np.inf, -1
             else:
                 Xe = X if mask is None else X[mask]
-                bo, bi, _ = obj.poll(Xe, cons3) if dev_cons is None else obj.poll(Xe, cons3, dev_cons)
+                if dev_motion is not None:
+                    bo, bi, _ = obj.poll(Xe, cons3, dev_cons, dev_motion)
+                else:
+                    bo, bi, _ = obj.poll(Xe, cons3) if dev_cons is None else obj.poll(Xe, cons3, dev_cons)
                 if mask is not None and bi >= 0:
                     bi = int(np.flatnonzero(mask)[bi])
             res.status.function_evaluations += X.shape[0]

@@ -76,6 +76,8 @@ EXPORTS = (
     "mac_poll_best_cons_dev_f64", "mac_mads_run_cons", "mac_mads_begin_cons",
     "mac_set_regions", "mac_regions_ingested", "mac_region_stats_f64",
     "mac_mads_run_opts", "mac_mads_begin_opts",
+    "mac_cons_mask_motion_f64", "mac_poll_best_motion_f64", "mac_motion_thresholds",
+    "mac_mads_run_motion", "mac_mads_begin_motion",
 )
 
 MAC_REGIONS_MAX = 64
@@ -170,6 +172,60 @@ def make_cons(cons=None, d_sep: float | None = None, zone_y: float | None = None
                 nan if zone_r is None else float(zone_r))
 
 
+class Motion(ctypes.Structure):
+    """mac_motion (include/maxcover.h): the target-motion constraints cons4 (cone_cos, with vel),
+    cons5 (v_max) and cons6 (a_max, with speed_prev) around the previous target ``anchor``. A NaN
+    scalar or a NULL array switches its constraint off. Built by make_motion, which keeps the arrays
+    alive on the object."""
+    _fields_ = [("anchor", ctypes.POINTER(ctypes.c_double)), ("vel", ctypes.POINTER(ctypes.c_double)),
+                ("speed_prev", ctypes.POINTER(ctypes.c_double)), ("cone_cos", ctypes.c_double),
+                ("v_max", ctypes.c_double), ("a_max", ctypes.c_double)]
+
+
+def make_motion(motion=None, anchor=None, vel=None, speed_prev=None, cone_cos: float | None = None,
+                v_max: float | None = None, a_max: float | None = None) -> Motion | None:
+    """A Motion from a Motion, a mapping / object with anchor, vel, speed_prev, cone_cos, v_max,
+    a_max fields (missing: off), or the keyword values; None stays None (all constraints off).
+    anchor: 3N [x; y; R]; vel: 2N [vx; vy]; speed_prev: N."""
+    if isinstance(motion, Motion):
+        return motion
+    if motion is not None:
+        get = motion.get if hasattr(motion, "get") else lambda k, d=None: getattr(motion, k, d)
+        anchor, vel, speed_prev = get("anchor"), get("vel"), get("speed_prev")
+        cone_cos, v_max, a_max = get("cone_cos"), get("v_max"), get("a_max")
+    elif anchor is None:
+        return None
+    nan = float("nan")
+    keep = [None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())
+            for a in (anchor, vel, speed_prev)]
+    if keep[0] is None:
+        raise ValueError("a motion constraint needs its anchor")
+    N, rem = divmod(keep[0].size, 3)
+    if rem or (keep[1] is not None and keep[1].size != 2 * N) or \
+            (keep[2] is not None and keep[2].size != N):
+        raise ValueError("motion: anchor is 3N, vel 2N and speed_prev N values")
+    dp = ctypes.POINTER(ctypes.c_double)
+    m = Motion(*[a.ctypes.data_as(dp) if a is not None else None for a in keep],
+               nan if cone_cos is None else float(cone_cos), nan if v_max is None else float(v_max),
+               nan if a_max is None else float(a_max))
+    m._keep = keep   # the arrays the pointers refer to
+    m.n_uav = N
+    return m
+
+
+def motion_thresholds(speed_prev: float, a_max: float) -> tuple[float, float]:
+    """mac_motion_thresholds: cons6 for one UAV as (q_hi, q_lo): infeasible iff q3 > q_hi or
+    q3 <= q_lo, with q3 the squared 3-D move."""
+    hi, lo = ctypes.c_double(), ctypes.c_double()
+    load_library().mac_motion_thresholds(float(speed_prev), float(a_max), ctypes.byref(hi),
+                                         ctypes.byref(lo))
+    return hi.value, lo.value
+
+
+def _opt(s):
+    return ctypes.byref(s) if s is not None else None
+
+
 class MaxCoverError(RuntimeError):
     """Non-zero status from libmaxcover (message from mac_last_error)."""
 
@@ -260,6 +316,20 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_mads_begin_opts": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                                  ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
                                  ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts)], _i32),
+        "mac_cons_mask_motion_f64": ([_vp, _dp, _i64, _i64, ctypes.POINTER(Cons), _u8p,
+                                      ctypes.POINTER(Motion)], _i32),
+        "mac_poll_best_motion_f64": ([_vp, _dp, _i64, _i64, _dp, ctypes.c_double, _dp, _dp,
+                                      ctypes.c_double, _dp, _dp, _i64p, ctypes.POINTER(Cons),
+                                      ctypes.POINTER(Motion)], _i32),
+        "mac_motion_thresholds": ([ctypes.c_double, ctypes.c_double, _dp, _dp], None),
+        "mac_mads_run_motion": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                                 ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats),
+                                 ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
+                                 ctypes.POINTER(Motion)], _i32),
+        "mac_mads_begin_motion": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                                   ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
+                                   ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
+                                   ctypes.POINTER(Motion)], _i32),
         "mac_append_points_dev_f64": ([_vp, _vp, _vp, _vp, _i64], _i32),
         "mac_fire_last_error": ([], ctypes.c_char_p),
         "mac_fire_thresholds": ([ctypes.POINTER(FireParams), _dp], None),
@@ -685,15 +755,22 @@ class Context:
                                                float(penalty), _ptr(out)))
         return out
 
-    def cons_mask(self, cands, cons) -> np.ndarray:
+    def cons_mask(self, cands, cons, motion=None) -> np.ndarray:
         """mac_cons_mask_f64: the feasibility of each candidate (K x 3N rows) under ``cons`` (a Cons,
-        or anything make_cons takes; None: all feasible), as a bool array. No point list needed."""
+        or anything make_cons takes; None: all feasible), as a bool array. No point list needed.
+        ``motion`` (a Motion, or anything make_motion takes): the target-motion constraints as well
+        (mac_cons_mask_motion_f64)."""
         c = _f64(cands)
         if c.ndim != 2:
             raise ValueError("cands must be K x 3N")
         K, three_n = c.shape
         out = np.zeros(max(K, 1), dtype=np.uint8)
         cs = make_cons(cons)
+        if motion is not None:
+            mo = make_motion(motion)
+            _check(self._L.mac_cons_mask_motion_f64(self._h, _ptr(c), three_n, K, _opt(cs),
+                                                    out.ctypes.data_as(_u8p), _opt(mo)))
+            return out[:K].astype(bool)
         _check(self._L.mac_cons_mask_f64(self._h, _ptr(c), three_n, K,
                                          ctypes.byref(cs) if cs is not None else None,
                                          out.ctypes.data_as(_u8p)))
@@ -707,10 +784,11 @@ class Context:
                                              _devptr(d_feasible), _stream(stream, self.device)))
 
     def poll_best(self, cands, r_max, penalty: float = 1e5, prev=None, d_lim=None,
-                  tan_half_fov: float = 1.0, want_all: bool = False, cons=None):
+                  tan_half_fov: float = 1.0, want_all: bool = False, cons=None, motion=None):
         """Returns (best_obj, best_idx[, objectives]); best_idx = -1 if none feasible. ``cons`` (a
         Cons, or anything make_cons takes): the swarm constraints applied on the device
-        (mac_poll_best_cons_f64); None keeps the plain call."""
+        (mac_poll_best_cons_f64); None keeps the plain call. ``motion`` (a Motion, or anything
+        make_motion takes): the target-motion constraints as well (mac_poll_best_motion_f64)."""
         c = _f64(cands)
         K, three_n = c.shape
         rm = _f64(r_max)
@@ -723,7 +801,10 @@ class Context:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), _ptr(objs) if objs is not None else None,
                 ctypes.byref(bo), ctypes.byref(bi))
-        if cons is None:
+        if motion is not None:
+            cs, mo = make_cons(cons), make_motion(motion)
+            _check(self._L.mac_poll_best_motion_f64(*args, _opt(cs), _opt(mo)))
+        elif cons is None:
             _check(self._L.mac_poll_best_f64(*args))
         else:
             cs = make_cons(cons)
@@ -815,12 +896,14 @@ class Context:
     # -- native MADS driver
     def mads_run(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                  tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-                 seed: int = 20250216, cons=None, poll_vars: str = "xyr"):
+                 seed: int = 20250216, cons=None, poll_vars: str = "xyr", motion=None):
         """mac_mads_run: the whole MADS loop in libmaxcover (candidates generated on the device).
         ``cons`` (a Cons, or anything make_cons takes, e.g. TDM_Constraints.merge_mac_cons's
         mapping): the swarm constraints every poll applies on the device (mac_mads_run_cons); None
         keeps the plain call. ``poll_vars``: "xyr" polls every variable (the calls above), "xy"
-        x and y only with the radii held (mac_mads_run_opts, MAC_POLL_XY). Returns (x, stats dict)."""
+        x and y only with the radii held (mac_mads_run_opts, MAC_POLL_XY). ``motion`` (a Motion, or
+        anything make_motion takes): the target-motion constraints on every poll
+        (mac_mads_run_motion). Returns (x, stats dict)."""
         pvars = poll_vars_code(poll_vars)
         x = _f64(x0)
         rm = _f64(r_max)
@@ -833,7 +916,10 @@ class Context:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), _ptr(out), ctypes.byref(st))
         cs = make_cons(cons)
-        if pvars != MAC_POLL_XYR:
+        if motion is not None:
+            op, mo = MadsOpts(pvars), make_motion(motion)
+            _check(self._L.mac_mads_run_motion(*args, _opt(cs), ctypes.byref(op), _opt(mo)))
+        elif pvars != MAC_POLL_XYR:
             op = MadsOpts(pvars)
             _check(self._L.mac_mads_run_opts(*args, ctypes.byref(cs) if cs is not None else None,
                                              ctypes.byref(op)))
@@ -846,13 +932,14 @@ class Context:
     def mads_stepper(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                      tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2,
                      ell_max: int = 6, seed: int = 20250216, shard=None,
-                     cons=None, poll_vars: str = "xyr") -> "MadsStepper":
+                     cons=None, poll_vars: str = "xyr", motion=None) -> "MadsStepper":
         """mac_mads_begin: the native loop one poll at a time over the candidate shard
         ``shard`` = (lo, hi) of each poll's 2 n_p candidates (None: the whole poll). ``cons``: as
         mads_run's (mac_mads_begin_cons; every rank of a sharded loop passes the same one).
-        ``poll_vars``: as mads_run's (n_p = 3N for "xyr", 2N for "xy": mac_mads_begin_opts)."""
+        ``poll_vars``: as mads_run's (n_p = 3N for "xyr", 2N for "xy": mac_mads_begin_opts).
+        ``motion``: as mads_run's (mac_mads_begin_motion; the same on every rank)."""
         st = MadsStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
-                         ell_max, seed, shard, cons, poll_vars)
+                         ell_max, seed, shard, cons, poll_vars, motion)
         self._steppers.add(st)
         return st
 
@@ -1053,7 +1140,7 @@ class MadsStepper:
     (0, candidates)."""
 
     def __init__(self, ctx: Context, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter,
-                 ell0, ell_max, seed, shard, cons=None, poll_vars: str = "xyr"):
+                 ell0, ell_max, seed, shard, cons=None, poll_vars: str = "xyr", motion=None):
         pvars = poll_vars_code(poll_vars)
         self._L = ctx._L
         self._ctx = ctx   # keeps the context alive while the stepper lives
@@ -1073,7 +1160,10 @@ class MadsStepper:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), lo, hi, ctypes.byref(h))
         cs = make_cons(cons)
-        if pvars != MAC_POLL_XYR:
+        if motion is not None:
+            op, mo = MadsOpts(pvars), make_motion(motion)
+            _check(self._L.mac_mads_begin_motion(*args, _opt(cs), ctypes.byref(op), _opt(mo)))
+        elif pvars != MAC_POLL_XYR:
             op = MadsOpts(pvars)
             _check(self._L.mac_mads_begin_opts(*args, ctypes.byref(cs) if cs is not None else None,
                                                ctypes.byref(op)))

@@ -36,6 +36,21 @@
 // UAV meets its own cell and the next one or two; with dcut = +inf all UAVs share cell 0 and every
 // pair is tested. No finite UAV is lost: each takes one slot of its cell from an atomic cursor. The
 // order inside a cell depends on the atomics; the result, an OR over pairs, does not.
+//
+// The target-motion constraints (mac_motion, include/maxcover.h) are per UAV and per candidate. With
+// the anchor a (the previous target) and t = (x_i - a.x_i, y_i - a.y_i, r_i - a.r_i),
+// q2 = fl(fl(tx*tx) + fl(ty*ty)) and q3 = fl(q2 + fl(tz*tz)), a candidate is infeasible iff some i has
+//   cons5 (:106-119)  fl(sqrt q3) > v_max                <=>  q3 > dlim_threshold(v_max)
+//   cons6 (:122-138)  |fl(sqrt q3) - p_i| > a_max        <=>  q3 > Qhi_i || q3 <= Qlo_i
+//   cons4 (:78-103)   fl(dot(u_i, t.xy) / fl(|u_i| * fl(sqrt q2))) < cone_cos
+// Qhi_i / Qlo_i are built on the host (motion_thresholds below): fl(s - p) is monotone in
+// s = fl(sqrt q3), so "fl(s - p) > a" holds from one double s_hi on, i.e. iff !(s < s_hi) iff
+// q3 > T(s_hi); "fl(p - s) > a" holds up to one double s_lo, i.e. iff s < next_up(s_lo) iff
+// q3 <= T(next_up(s_lo)). |u_i| = fl(sqrt(fl(ux*ux) + fl(uy*uy))) comes from the host as well. cons4
+// alone needs a square root and a division on the device (both fp64, correctly rounded without
+// fast-math); a zero velocity or a zero move gives 0/0 = NaN, which no comparison rejects. The tests
+// sit in cons_violates' loader (MOT, a compile-time flag: the instantiations without it are the code
+// they were); with d_sep off there is no sort at all (motion_violates).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -85,13 +100,114 @@ static inline ConsArgs cons_args(double d_sep, double zone_y, double zone_r)
     return a;
 }
 
+// The motion constraints' device arguments: per-UAV arrays (one upload per call or stepper) and the
+// scalars. A constraint that is off has its flag 0 and its arrays unread.
+struct MotionArgs {
+    const double* anchor;   // 3N: [x; y; R] of the previous target
+    const double* vel;      // 2N: [vx; vy]                              (cons4)
+    const double* un;       // N: fl(sqrt(fl(vx*vx) + fl(vy*vy)))         (cons4)
+    const double* qhi;      // N: infeasible iff q3 > qhi[i] ...          (cons6)
+    const double* qlo;      // N: ... or q3 <= qlo[i]
+    double cone_cos;        // cons4: infeasible iff c < cone_cos
+    double q5;              // cons5: infeasible iff q3 > q5 = dlim_threshold(v_max)
+    int cone, speed, accel;
+};
+
+// Doubles s >= 0 in their order, by bit pattern: 0 .. kMotionInfBits (+inf).
+constexpr uint64_t kMotionInfBits = 0x7ff0000000000000ull;
+
+// cons6's thresholds for one UAV (p = speed_prev[i], a = a_max; a NaN in either: neither side ever
+// rejects): see the header. The two
+// boundaries are found by bisection over the non-negative doubles (the predicates are monotone in
+// s because a correctly rounded subtraction is), so they are exact whatever p and a are.
+//   qhi = T(s_hi), s_hi the smallest s in [0, +inf] with fl(s - p) > a   (+inf when there is none)
+//   qlo = T(next_up(s_lo)), s_lo the largest s in [0, +inf] with fl(p - s) > a   (-1 when none)
+static inline void motion_thresholds(double p, double a, double* qhi, double* qlo)
+{
+    auto dbl = [](uint64_t b) { return __builtin_bit_cast(double, b); };
+    auto up = [&](uint64_t b) { const volatile double d = dbl(b) - p; return d > a; };
+    auto dn = [&](uint64_t b) { const volatile double d = p - dbl(b); return d > a; };
+    *qhi = __builtin_inf();
+    *qlo = -1.0;
+    if (p != p || a != a) return;   // every comparison false
+    // p = +inf makes fl(s - p) NaN at s = +inf only: the search runs over the finite s and +inf is
+    // looked at on its own
+    if (up(0)) {
+        *qhi = cover_threshold(0.0);   // -1: every q3 that is not NaN
+    } else {
+        uint64_t lo = 0, hi = kMotionInfBits - 1;   // up(lo) false; hi: the largest finite
+        if (up(hi)) {
+            while (hi - lo > 1) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (up(mid)) hi = mid; else lo = mid;
+            }
+            *qhi = cover_threshold(dbl(hi));
+        } else if (up(kMotionInfBits)) {
+            *qhi = cover_threshold(__builtin_inf());   // DBL_MAX: q3 = +inf only
+        }
+    }
+    if (dn(0)) {
+        uint64_t lo = 0, hi = kMotionInfBits;   // dn(lo) true
+        if (dn(hi)) {
+            lo = hi;
+        } else {
+            while (hi - lo > 1) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (dn(mid)) lo = mid; else hi = mid;
+            }
+        }
+        // s <= s_lo  <=>  s < next_up(s_lo)  <=>  q3 <= T(next_up(s_lo)); s_lo = +inf: every q3
+        *qlo = lo == kMotionInfBits ? __builtin_inf() : cover_threshold(next_up(dbl(lo)));
+    }
+}
+
+// The motion tests of UAV e at (x, y, r) (r is read only under cons5 / cons6).
+__device__ __forceinline__ bool motion_rejects(const MotionArgs& m, int e, int N, double x, double y, double r)
+{
+    const double tx = x - m.anchor[e], ty = y - m.anchor[N + e];
+    const double q2 = tx * tx + ty * ty;
+    bool bad = false;
+    if (m.speed | m.accel) {
+        const double tz = r - m.anchor[2 * N + e];
+        const double q3 = q2 + tz * tz;
+        bad = m.speed && q3 > m.q5;
+        if (m.accel) bad |= q3 > m.qhi[e] || q3 <= m.qlo[e];
+    }
+    if (m.cone) {
+        const double ux = m.vel[e], uy = m.vel[N + e];
+        const double c = (ux * tx + uy * ty) / (m.un[e] * __builtin_sqrt(q2));
+        bad |= c < m.cone_cos;
+    }
+    return bad;
+}
+
+// A candidate under the motion constraints (and cons7) with d_sep off: no pair test, so no sort, no
+// extent reduction and no LDS arrays. A load, the tests and one flag.
+template <int S, class Load>
+__device__ __forceinline__ bool motion_violates(Load load, int N, const ConsArgs& a, const MotionArgs& m)
+{
+    bool bad = false;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const int e = s * kConsBlock + (int)threadIdx.x;
+        if (e < N) {
+            double x, y, r;
+            load(e, x, y, r);
+            bad |= a.zone && y < a.zone_y && r > a.zone_r;
+            bad |= motion_rejects(m, e, N, x, y, r);
+        }
+    }
+    return __syncthreads_or(bad ? 1 : 0) != 0;
+}
+
 // The sort-and-sweep of one candidate by one workgroup, shared by the matrix and the generated-poll
 // kernels: load(e, x, y, r) gives UAV e's values (r is read only under cons7). Thread t loads
 // elements s * 256 + t (s < S, 256 S >= N) and owns cell t of the kConsCells cells. Dynamic LDS:
 // 17 * 256 S bytes (x, y and the cell of every sorted position). Returns (thread 0's value is the
 // candidate's) whether a constraint rejects the candidate.
-template <int S, class Load>
-__device__ __forceinline__ bool cons_violates(Load load, int N, const ConsArgs& a)
+// MOT: the motion tests (*m) beside cons7 in the loader.
+template <int S, bool MOT = false, class Load>
+__device__ __forceinline__ bool cons_violates(Load load, int N, const ConsArgs& a, const MotionArgs* m = nullptr)
 {
     static_assert(kConsCells == kConsBlock, "one cell per thread");
     constexpr int P = kConsBlock * S;
@@ -121,6 +237,7 @@ __device__ __forceinline__ bool cons_violates(Load load, int N, const ConsArgs& 
             double x, y, r;
             load(e, x, y, r);
             bad |= a.zone && y < a.zone_y && r > a.zone_r;
+            if constexpr (MOT) bad |= motion_rejects(*m, e, N, x, y, r);
             if (__builtin_fabs(x) < inf && __builtin_fabs(y) < inf) {
                 kx[s] = x;
                 ky[s] = y;
@@ -247,6 +364,26 @@ __global__ __launch_bounds__(kConsBlock) void cons_mask_kernel(const double* __r
     if (threadIdx.x == 0) feasible[blockIdx.x] = v ? 0 : 1;
 }
 
+// The same under a mac_motion. SEP: cons8 is on (the sort and its dynamic LDS); else motion_violates.
+template <int S, bool SEP>
+__global__ __launch_bounds__(kConsBlock) void cons_mask_motion_kernel(const double* __restrict__ cands, int N,
+                                                                    ConsArgs a, MotionArgs m,
+                                                                    uint8_t* __restrict__ feasible)
+{
+    const double* __restrict__ c = cands + (size_t)blockIdx.x * (size_t)(3 * N);
+    auto load = [&](int e, double& x, double& y, double& r) {
+        x = c[e];
+        y = c[N + e];
+        r = c[2 * N + e];
+    };
+    bool v;
+    if constexpr (SEP)
+        v = cons_violates<S, true>(load, N, a, &m);
+    else
+        v = motion_violates<S>(load, N, a, m);
+    if (threadIdx.x == 0) feasible[blockIdx.x] = v ? 0 : 1;
+}
+
 // The mask over a generated poll (the native MADS driver, k_prep.h CandSrc): workgroup = candidate k
 // of the source (a rank's shard: candidate src.k0 + k of the poll), its x and y drawn through
 // src.get, r only under cons7. One byte per candidate of the shard, read by the poll's prep launch
@@ -266,6 +403,31 @@ __global__ __launch_bounds__(kConsBlock) void cons_mask_gen_kernel(uint64_t* ts,
                 r = a.zone ? src.get(k, 2 * N + e, N) : 0.0;
             },
             N, a);
+        if (threadIdx.x == 0) feasible[k] = v ? 0 : 1;
+    }
+    ts_end(ts);
+}
+
+// The same under a mac_motion: r is drawn under cons5, cons6 or cons7.
+template <int S, bool SEP>
+__global__ __launch_bounds__(kConsBlock) void cons_mask_gen_motion_kernel(uint64_t* ts, CandSrc src, int N,
+                                                                        ConsArgs a, MotionArgs m,
+                                                                        uint8_t* __restrict__ feasible)
+{
+    ts_begin(ts);   // profiling only (k_common.h)
+    if (src.resolve(true)) {
+        const int k = (int)blockIdx.x;
+        const bool need_r = a.zone | m.speed | m.accel;
+        auto load = [&](int e, double& x, double& y, double& r) {
+            x = src.get(k, e, N);
+            y = src.get(k, N + e, N);
+            r = need_r ? src.get(k, 2 * N + e, N) : 0.0;
+        };
+        bool v;
+        if constexpr (SEP)
+            v = cons_violates<S, true>(load, N, a, &m);
+        else
+            v = motion_violates<S>(load, N, a, m);
         if (threadIdx.x == 0) feasible[k] = v ? 0 : 1;
     }
     ts_end(ts);

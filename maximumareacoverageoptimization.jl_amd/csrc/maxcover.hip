@@ -173,6 +173,8 @@ struct Lane {
     DevBuf clv;                                // closure candidates written by the host (BAR)
     DevBuf bdpart, bdarrive, bdout;            // by_disk_kernel: owned words, arrivals; host calls' results
     DevBuf cmask, cbest;                       // masked poll (k_cons.h): feasibility bytes; the chain's own best
+    DevBuf motion;                             // mac_motion's per-UAV arrays (k_cons.h MotionArgs): 8N doubles
+    std::vector<double> h_motion;              // ... as built on the host
     DevBuf prec, cost;                         // prep launch: per-disk records; walk costs
     int um_hist[8] = {};                       // most distinct positions of a disk, last 8 polls
     int walk_hist[8] = {};                     // the walk AUTO would have chosen, last 8 polls
@@ -661,7 +663,7 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                          double tan_half_fov, double* d_area, double* d_obj, double* d_best,
                          int64_t idx_base, uint64_t* d_mirror = nullptr, uint64_t mirror_seq = 0,
                          const FinBest* fb_mads = nullptr, unsigned long long* d_feas = nullptr,
-                         const ConsArgs* gcons = nullptr)
+                         const ConsArgs* gcons = nullptr, const MotionArgs* gmot = nullptr)
 {
     const int64_t M = ctx->M;
     int n_poll = N, n_other = 1;
@@ -732,12 +734,23 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
         L->cmask.reserve((size_t)K);
         d_mask8 = L->cmask.as<uint8_t>();
         const int S = cons_slots(N);   // UAVs per thread: 1, 2, 4, 8 (N <= kConsMaxN, checked at begin)
-        void (*const kern)(uint64_t*, CandSrc, int, ConsArgs, uint8_t*) =
-            S == 1 ? cons_mask_gen_kernel<1> : S == 2 ? cons_mask_gen_kernel<2>
-          : S == 4 ? cons_mask_gen_kernel<4> : cons_mask_gen_kernel<8>;
         uint64_t* tsm = take_ts(K, ts_m, ts_nm);
-        hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock), (uint32_t)(17 * kConsBlock * S), s, tsm,
-                           src, N, *gcons, L->cmask.as<uint8_t>());
+        if (gmot) {   // ... and the motion constraints: with d_sep off, no sort and no LDS arrays
+            void (*const kern)(uint64_t*, CandSrc, int, ConsArgs, MotionArgs, uint8_t*) =
+                gcons->sep ? (S == 1 ? cons_mask_gen_motion_kernel<1, true> : S == 2 ? cons_mask_gen_motion_kernel<2, true>
+                            : S == 4 ? cons_mask_gen_motion_kernel<4, true> : cons_mask_gen_motion_kernel<8, true>)
+                           : (S == 1 ? cons_mask_gen_motion_kernel<1, false> : S == 2 ? cons_mask_gen_motion_kernel<2, false>
+                            : S == 4 ? cons_mask_gen_motion_kernel<4, false> : cons_mask_gen_motion_kernel<8, false>);
+            hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock),
+                               gcons->sep ? (uint32_t)(17 * kConsBlock * S) : 0u, s, tsm, src, N, *gcons, *gmot,
+                               L->cmask.as<uint8_t>());
+        } else {
+            void (*const kern)(uint64_t*, CandSrc, int, ConsArgs, uint8_t*) =
+                S == 1 ? cons_mask_gen_kernel<1> : S == 2 ? cons_mask_gen_kernel<2>
+              : S == 4 ? cons_mask_gen_kernel<4> : cons_mask_gen_kernel<8>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock), (uint32_t)(17 * kConsBlock * S), s, tsm,
+                               src, N, *gcons, L->cmask.as<uint8_t>());
+        }
         HCK(hipGetLastError());
     }
 
@@ -1325,18 +1338,77 @@ static bool cons_active(const mac_cons* cons, ConsArgs* a)
     return a->sep || a->zone;
 }
 
+// Which motion constraints of a mac_motion are on (a scalar that is NaN or a NULL array: off).
+static bool motion_on(const mac_motion* mo, bool* cone, bool* speed, bool* accel)
+{
+    *cone = *speed = *accel = false;
+    if (!mo || !mo->anchor) return false;
+    *cone = mo->cone_cos == mo->cone_cos && mo->vel;
+    *speed = mo->v_max == mo->v_max;
+    *accel = mo->a_max == mo->a_max && mo->speed_prev;
+    return *cone || *speed || *accel;
+}
+
+// The kernels' arguments from a mac_motion with a constraint on: the per-UAV arrays built on the
+// host (k_cons.h MotionArgs: anchor, vel, |vel|, cons6's thresholds) and uploaded into the lane's
+// buffer on s. The host copies are read before the call returns.
+static MotionArgs motion_upload(Lane* L, hipStream_t s, int N, const mac_motion* mo)
+{
+    bool cone, speed, accel;
+    motion_on(mo, &cone, &speed, &accel);
+    MotionArgs m{};
+    m.cone = cone;
+    m.speed = speed;
+    m.accel = accel;
+    m.cone_cos = mo->cone_cos;
+    m.q5 = speed ? dlim_threshold(mo->v_max) : __builtin_inf();
+    const size_t n = (size_t)N;
+    std::vector<double>& h = L->h_motion;
+    h.assign(8 * n, 0.0);
+    std::copy(mo->anchor, mo->anchor + 3 * n, h.begin());
+    if (cone) {
+        std::copy(mo->vel, mo->vel + 2 * n, h.begin() + 3 * n);
+        for (size_t i = 0; i < n; ++i) {
+            const double ux = mo->vel[i], uy = mo->vel[n + i];
+            h[5 * n + i] = std::sqrt(ux * ux + uy * uy);
+        }
+    }
+    if (accel)
+        for (size_t i = 0; i < n; ++i) motion_thresholds(mo->speed_prev[i], mo->a_max, &h[6 * n + i], &h[7 * n + i]);
+    L->motion.reserve(sizeof(double) * 8 * std::max<size_t>(n, 1));
+    HCK(hipMemcpyAsync(L->motion.p, h.data(), sizeof(double) * 8 * n, hipMemcpyHostToDevice, s));
+    HCK(hipStreamSynchronize(s));   // (pageable source: the copy is done with h before anyone refills it)
+    const double* d = L->motion.as<double>();
+    m.anchor = d;
+    m.vel = d + 3 * n;
+    m.un = d + 5 * n;
+    m.qhi = d + 6 * n;
+    m.qlo = d + 7 * n;
+    return m;
+}
+
 static void cons_mask_enqueue(hipStream_t s, const double* d_cands, int N, int64_t K, const ConsArgs& a,
-                              uint8_t* d_feas)
+                              uint8_t* d_feas, const MotionArgs* mot = nullptr)
 {
     constexpr int64_t kMaxWG = (int64_t)1 << 23;   // workgroups per launch (2^31 threads)
     const int S = cons_slots(N);                   // UAVs per thread: 1, 2, 4, 8 (N <= 2048)
     void (*const kern)(const double*, int, ConsArgs, uint8_t*) =
         S == 1 ? cons_mask_kernel<1> : S == 2 ? cons_mask_kernel<2> : S == 4 ? cons_mask_kernel<4> : cons_mask_kernel<8>;
-    const uint32_t lds = (uint32_t)(17 * kConsBlock * S);   // x, y, cell per sorted position
+    // under a mac_motion: with d_sep off, the kernel without the sort and its LDS arrays
+    void (*const kmot)(const double*, int, ConsArgs, MotionArgs, uint8_t*) =
+        a.sep ? (S == 1 ? cons_mask_motion_kernel<1, true> : S == 2 ? cons_mask_motion_kernel<2, true>
+               : S == 4 ? cons_mask_motion_kernel<4, true> : cons_mask_motion_kernel<8, true>)
+              : (S == 1 ? cons_mask_motion_kernel<1, false> : S == 2 ? cons_mask_motion_kernel<2, false>
+               : S == 4 ? cons_mask_motion_kernel<4, false> : cons_mask_motion_kernel<8, false>);
+    const uint32_t lds = (mot && !a.sep) ? 0u : (uint32_t)(17 * kConsBlock * S);   // x, y, cell per sorted position
     for (int64_t k0 = 0; k0 < K; k0 += kMaxWG) {
         const int64_t B = std::min(kMaxWG, K - k0);
-        hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kConsBlock), lds, s,
-                           d_cands + (size_t)k0 * (size_t)(3 * N), N, a, d_feas + k0);
+        if (mot)
+            hipLaunchKernelGGL(kmot, dim3((unsigned)B), dim3(kConsBlock), lds, s,
+                               d_cands + (size_t)k0 * (size_t)(3 * N), N, a, *mot, d_feas + k0);
+        else
+            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kConsBlock), lds, s,
+                               d_cands + (size_t)k0 * (size_t)(3 * N), N, a, d_feas + k0);
         HCK(hipGetLastError());
     }
 }
@@ -1357,7 +1429,7 @@ static int32_t host_eval(mac_ctx* ctx, const T* cands, int64_t three_n, int64_t 
                          const double* r_max, double penalty, const T* prev,
                          const double* d_lim, double tan_half_fov, double* area_out,
                          double* obj_out, double* best_obj, int64_t* best_idx,
-                         const ConsArgs* cons = nullptr)
+                         const ConsArgs* cons = nullptr, const mac_motion* motion = nullptr)
 {
     constexpr bool f32 = std::is_same<T, float>::value;
     int32_t rc = check_common(ctx, three_n, K);
@@ -1435,7 +1507,9 @@ static int32_t host_eval(mac_ctx* ctx, const T* cands, int64_t three_n, int64_t 
     const bool tiled = use_tiled(ctx, N, hc, three_n);
     if (cons) {
         L->cmask.reserve((size_t)K);
-        cons_mask_enqueue(s, L->cands.as<double>(), N, K, *cons, L->cmask.as<uint8_t>());
+        MotionArgs mot{};
+        if (motion) mot = motion_upload(L, s, N, motion);   // (mac_poll_best_motion_f64: a constraint is on)
+        cons_mask_enqueue(s, L->cands.as<double>(), N, K, *cons, L->cmask.as<uint8_t>(), motion ? &mot : nullptr);
     }
     enqueue_eval(ctx, L, s, matrix_src(L->cands.as<double>(), N), N, (int)K, tiled, d_rmax, penalty, d_prev,
                  d_dlimT, d_prev ? L->dlimraw.as<double>() : nullptr, tan_half_fov,
@@ -1897,7 +1971,8 @@ void mac_ctx_destroy(mac_ctx* ctx)
                           &l->lanexp, &l->rows, &l->nboxT, &l->cnt, &l->dlimraw, &l->finblk, &l->finarrive, &l->c32, &l->p32,
                           &l->cpart, &l->carrive, &l->ctot, &l->clv, &l->prec, &l->cost, &l->nboxU,
                           &l->ncountU, &l->orjobs, &l->pd, &l->dead8, &l->frows, &l->fwhint, &l->fwlist, &l->fwcount,
-                          &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout, &l->cmask, &l->cbest})
+                          &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout, &l->cmask, &l->cbest,
+                          &l->motion})
             b->release();
         if (l->done) (void)hipEventDestroy(l->done);
 
@@ -2477,6 +2552,8 @@ struct mac_mads {
     const double* d_dlimT = nullptr;
     ConsArgs cons{};              // the swarm constraints (mac_mads_begin_cons): every poll's mask launch
     bool has_cons = false;
+    MotionArgs mot{};             // the motion constraints (mac_mads_begin_motion): the mask launch's tests;
+    bool has_mot = false;         // has_cons is set with them (the arrays: the lane's motion buffer)
     std::vector<double> x;
     double f = INFINITY;
     int64_t evals = 0, it = 0, rejected = 0, succ = 0;
@@ -2596,7 +2673,8 @@ static void mads_best_of(mac_mads* m, const CandSrc& src, int Kc, int64_t idx_ba
                  m->d_prev ? m->L->dlimraw.as<double>() : nullptr, m->tan_half_fov,
                  nullptr, m->L->obj.as<double>(), mads_best_ptr(m), idx_base,
                  slot ? m->d_slot : nullptr, slot ? ++m->seq : 0, nullptr,
-                 slot ? m->d_feas.as<unsigned long long>() : nullptr, m->has_cons ? &m->cons : nullptr);
+                 slot ? m->d_feas.as<unsigned long long>() : nullptr, m->has_cons ? &m->cons : nullptr,
+                 m->has_mot ? &m->mot : nullptr);
     if (!slot) HCK(hipMemcpyAsync(m->hb, mads_best_ptr(m), 16, hipMemcpyDeviceToHost, m->s));
 }
 
@@ -2661,7 +2739,8 @@ static int32_t mads_opts_check(const mac_mads_opts* opts, bool* xy)
 static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                                double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                                const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                               mac_mads** out, const mac_cons* cons, bool xy);
+                               mac_mads** out, const mac_cons* cons, bool xy,
+                               const mac_motion* motion = nullptr);
 
 int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
@@ -2696,7 +2775,7 @@ int32_t mac_mads_begin_opts(mac_ctx* ctx, const double* x0, int64_t three_n, con
 static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                                double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                                const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                               mac_mads** out, const mac_cons* cons, bool xy)
+                               mac_mads** out, const mac_cons* cons, bool xy, const mac_motion* motion)
 {
     ABI_BEGIN
     if (!out) return fail(MAC_E_INVAL, "null out");
@@ -2714,7 +2793,10 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
     if (shard_lo < 0 || shard_hi > K || shard_lo > shard_hi)
         return fail(MAC_E_INVAL, "shard outside [0, 2n)");
     ConsArgs ca{};
-    const bool has_cons = cons_active(cons, &ca);
+    bool mc, ms, ma;
+    const bool has_mot = motion_on(motion, &mc, &ms, &ma);
+    // (a motion constraint alone: the mask launch with cons7 and cons8 off)
+    const bool has_cons = cons_active(cons, &ca) | has_mot;
     if (has_cons && N > kConsMaxN)
         return fail(MAC_E_INVAL, "mac_mads_begin_cons: N = " + std::to_string(N) + " > " +
                                      std::to_string(kConsMaxN) + " UAVs under a swarm constraint");
@@ -2749,6 +2831,10 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
         HCK(hipMemcpyAsync(L->rmax.p, r_max, sizeof(double) * N, hipMemcpyHostToDevice, s));
         m->d_feas.reserve(sizeof(unsigned long long));
         HCK(hipMemsetAsync(m->d_feas.p, 0, sizeof(unsigned long long), s));
+        if (has_mot) {
+            m->mot = motion_upload(L, s, N, motion);
+            m->has_mot = true;
+        }
         if (prev) {
             m->h_prev.assign(prev, prev + three_n);
             L->prev.reserve(sizeof(double) * three_n);
@@ -2775,7 +2861,8 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
         mads_best_of(m, matrix_src(L->cands.as<double>(), N), 1, 0);
         if (has_cons) {   // ... or a swarm constraint: its byte from the matrix mask
             L->cmask.reserve(1);
-            cons_mask_enqueue(s, L->cands.as<double>(), N, 1, ca, L->cmask.as<uint8_t>());
+            cons_mask_enqueue(s, L->cands.as<double>(), N, 1, ca, L->cmask.as<uint8_t>(),
+                              has_mot ? &m->mot : nullptr);
         }
         HCK(hipStreamSynchronize(s));
         m->f = __builtin_bit_cast(int64_t, m->hb[1]) >= 0 ? m->hb[0] : INFINITY;
@@ -3167,7 +3254,7 @@ static void mads_run_pipelined(mac_mads* m)
                      m->d_prev, m->d_dlimT, m->d_prev ? m->L->dlimraw.as<double>() : nullptr,
                      m->tan_half_fov, nullptr, m->L->obj.as<double>(),
                      m->L->best.as<double>(), 0, m->d_slot, (uint64_t)t, &fbm, &dst->feas,
-                     m->has_cons ? &m->cons : nullptr);
+                     m->has_cons ? &m->cons : nullptr, m->has_mot ? &m->mot : nullptr);
         const auto t3 = clk::now();
         if (computed < n_iter) {   // one iteration's permutations per poll, uploaded per chunk
             perms_of(++computed);
@@ -3208,7 +3295,7 @@ int32_t mac_mads_run(mac_ctx* ctx, const double* x0, int64_t three_n, const doub
 static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                              const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                             bool xy);
+                             bool xy, const mac_motion* motion = nullptr);
 
 int32_t mac_mads_run_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                           double penalty, const double* prev, const double* d_lim, double tan_half_fov,
@@ -3240,14 +3327,14 @@ int32_t mac_mads_run_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const
 static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                              const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                             bool xy)
+                             bool xy, const mac_motion* motion)
 {
     ABI_BEGIN
     if (!x_out) return fail(MAC_E_INVAL, "null argument");
     mac_mads* m = nullptr;
     // the whole poll: every candidate of the 2 n_p (n_p = 3N, or 2N for the xy-only poll)
     int32_t rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
-                                 xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy);
+                                 xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy, motion);
     if (rc) return rc;
     if (mads_pipelinable(m)) {
         try {
@@ -4274,6 +4361,123 @@ int32_t mac_poll_best_cons_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t 
     if ((uintptr_t)d_best & 7) return fail(MAC_E_INVAL, "d_best not 8-byte aligned");
     return poll_best_dev<double>(ctx, d_cands, three_n, K, d_rmax, penalty, d_prev, d_dlim, tan_half_fov,
                                  idx_base, d_obj, d_best, stream, &a);
+    ABI_END
+}
+
+// ---- target-motion constraints (k_cons.h; include/maxcover.h mac_motion)
+
+void mac_motion_thresholds(double speed_prev, double a_max, double* q_hi, double* q_lo)
+{
+    double hi, lo;
+    motion_thresholds(speed_prev, a_max, &hi, &lo);
+    if (q_hi) *q_hi = hi;
+    if (q_lo) *q_lo = lo;
+}
+
+int32_t mac_cons_mask_motion_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                                 const mac_cons* cons, uint8_t* feasible_out, const mac_motion* motion)
+{
+    bool mc, ms, ma;
+    if (!motion_on(motion, &mc, &ms, &ma))   // nothing on: the plain call, untouched
+        return mac_cons_mask_f64(ctx, cands, three_n, K, cons, feasible_out);
+    ABI_BEGIN
+    int32_t rc = cons_check(ctx, cands, three_n, K, feasible_out);
+    if (rc || K == 0) return rc;
+    if (three_n == 0) {   // no UAV to violate anything
+        std::memset(feasible_out, 1, (size_t)K);
+        return MAC_OK;
+    }
+    ConsArgs a{};
+    cons_active(cons, &a);
+    const int N = (int)(three_n / 3);
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t in_bytes = sizeof(double) * (size_t)three_n * (size_t)K;
+    L->cands.reserve(in_bytes);
+    L->cmask.reserve((size_t)K);
+    const MotionArgs mot = motion_upload(L, s, N, motion);
+    const bool staged = in_bytes <= ((size_t)64 << 20);
+    if (staged) {
+        L->h_io.reserve(std::max<size_t>(in_bytes, 64));
+        staged_upload(cands, L->h_io.p, L->cands.p, in_bytes, s);
+    } else {
+        HCK(hipMemcpyAsync(L->cands.p, cands, in_bytes, hipMemcpyHostToDevice, s));
+    }
+    cons_mask_enqueue(s, L->cands.as<double>(), N, K, a, L->cmask.as<uint8_t>(), &mot);
+    if (staged && (size_t)K <= L->h_io.cap) {   // (the upload has completed before the kernel ran)
+        HCK(hipMemcpyAsync(L->h_io.p, L->cmask.p, (size_t)K, hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+        std::memcpy(feasible_out, L->h_io.p, (size_t)K);
+    } else {
+        HCK(hipMemcpyAsync(feasible_out, L->cmask.p, (size_t)K, hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+    }
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_poll_best_motion_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                                 const double* r_max, double penalty, const double* prev,
+                                 const double* d_lim, double tan_half_fov, double* obj_out,
+                                 double* best_obj, int64_t* best_idx, const mac_cons* cons,
+                                 const mac_motion* motion)
+{
+    bool mc, ms, ma;
+    if (!motion_on(motion, &mc, &ms, &ma))   // nothing on: the _cons call, untouched
+        return mac_poll_best_cons_f64(ctx, cands, three_n, K, r_max, penalty, prev, d_lim, tan_half_fov, obj_out,
+                                      best_obj, best_idx, cons);
+    ABI_BEGIN
+    if (!best_obj || !best_idx) return fail(MAC_E_INVAL, "null best output");
+    if (!r_max && three_n > 0) return fail(MAC_E_INVAL, "null r_max");
+    int32_t rc = check_common(ctx, three_n, K);
+    if (rc) return rc;
+    if (three_n / 3 > kConsMaxN)
+        return fail(MAC_E_INVAL, "mac_poll_best_motion: N = " + std::to_string(three_n / 3) + " > " +
+                                     std::to_string(kConsMaxN) + " UAVs (the constraint kernel's limit)");
+    ConsArgs a{};
+    cons_active(cons, &a);
+    return host_eval<double>(ctx, cands, three_n, K, r_max, penalty, prev, d_lim, tan_half_fov, nullptr,
+                             obj_out, best_obj, best_idx, &a, motion);
+    ABI_END
+}
+
+int32_t mac_mads_run_motion(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
+                            const mac_mads_opts* opts, const mac_motion* motion)
+{
+    bool mc, ms, ma;
+    if (!motion_on(motion, &mc, &ms, &ma))   // nothing on: the _opts call, untouched
+        return mac_mads_run_opts(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
+                                 cons, opts);
+    ABI_BEGIN
+    bool xy = false;
+    const int32_t rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons, xy,
+                         motion);
+    ABI_END
+}
+
+int32_t mac_mads_begin_motion(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                              const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi, mac_mads** out,
+                              const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion)
+{
+    bool mc, ms, ma;
+    if (!motion_on(motion, &mc, &ms, &ma))   // nothing on: the _opts call, untouched
+        return mac_mads_begin_opts(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
+                                   shard_hi, out, cons, opts);
+    ABI_BEGIN
+    if (!out) return fail(MAC_E_INVAL, "null out");
+    *out = nullptr;
+    bool xy = false;
+    const int32_t rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
+                           out, cons, xy, motion);
     ABI_END
 }
 
