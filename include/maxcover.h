@@ -485,6 +485,37 @@ int32_t mac_mads_begin_motion(mac_ctx* ctx, const double* x0, int64_t three_n, c
                               mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts,
                               const mac_motion* motion);
 
+/* The mesh of the native driver: DirectSearch's SetGranularity, the one setting the reference's
+ * optimize uses (src/TDM_STATIC_opt.jl:131-137; its commented variant keeps 1.0 on the positions and
+ * puts 0.1 on the radii). granularity points to 3N host doubles laid out as x (x_0.., y_0.., r_0..),
+ * each finite and > 0, copied during the call; NULL is 1.0 everywhere. Polled variable v moves by
+ * d = fl(g[v] * (double)L[rp[v]][cp[kk]]), L's entry the integer the stream draws without a mesh (one
+ * product), and a candidate's value is x[v] + d (k < n_p) or x[v] - d (k >= n_p): with g[v] = 1.0 the
+ * doubles of the calls above bit for bit. The stream, the permutations, the draws per iteration, the
+ * success / failure rule, ell_max and the stop at ell < 0 are unchanged; the whole-poll rejection
+ * (rejected_polls) tests variable v's diagonal step fl(g[v] * 2^ell). Under MAC_POLL_XY only
+ * g[0 .. 2N) is used (the radius entries are still validated). */
+typedef struct mac_mads_mesh {
+    const double* granularity;   /* 3N host doubles, or NULL (all 1.0) */
+    int64_t reserved;            /* 0 */
+} mac_mads_mesh;                 /* 16 B */
+/* mac_mads_run_motion / mac_mads_begin_motion on a mesh. mesh = NULL, granularity = NULL or every
+ * entry exactly 1.0: the _motion call itself — the same launches, outputs and statistics. A zero,
+ * negative, NaN or infinite entry or a non-zero reserved word: MAC_E_INVAL (the message names
+ * mac_mads_mesh), nothing written and *out cleared, checked before the context is touched. A stepper
+ * begun with a mesh uses it in every call that takes it (mac_mads_poll, _update, _poll_ahead,
+ * _advance, _result, _best_buffer); the ranks of a sharded loop pass the same vector. */
+int32_t mac_mads_run_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* params, double* x_out, mac_mads_stats* stats,
+                          const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
+                          const mac_mads_mesh* mesh);
+int32_t mac_mads_begin_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
+                            mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts,
+                            const mac_motion* motion, const mac_mads_mesh* mesh);
+
 /* fp32 candidates (config 3's "fp32" caller path; SURVEY 8(b) "*_f32: coords f32, accum f64"):
  * the candidate matrix (and prev) are uploaded as floats and widened exactly on the device;
  * coverage is then the reference's fp64 predicate on those doubles, areas accumulate in fp64 /
@@ -622,6 +653,12 @@ int32_t mac_profile_split(mac_ctx* ctx, double* prep_ms, double* walk_ms, double
  *   launch per masked poll) (MAC_PROF_ROLES = 10). */
 #define MAC_PROF_ROLES 10
 int32_t mac_profile_kernels(mac_ctx* ctx, double* ms_out, int64_t* launches_out, int32_t n_roles);
+/* With profiling on, the fused chain's launch-hint reports as the context's later enqueues read them
+ * (each poll's finalize writes its report to mapped host words; the lane's next poll reads them, so a
+ * report may be read twice or not at all: a sample, not a count of polls): the reports read, and the
+ * sum and the largest of hint word 1, the disks of a poll that took one position per candidate (keys
+ * that reproduce no double: the identity map). Any output may be NULL; reset != 0 clears the three. */
+int32_t mac_profile_fused(mac_ctx* ctx, int64_t* reports, int64_t* ident_sum, int64_t* ident_max, int32_t reset);
 
 /* ---- fire generator (src/DynamicArea.jl, config 5) ------------------------------ */
 /* Cellular-automaton forest fire on an nx x ny grid of dx x dy cells, cell (i, j) 1-based with

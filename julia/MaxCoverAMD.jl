@@ -18,7 +18,7 @@ is what the parity tests exercise. See INTEGRATION.md.
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacCons, MacMotion, cons_mask,
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacCons, MacMotion, cons_mask,
        set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
@@ -412,6 +412,27 @@ MadsOpts(poll_vars::Symbol) = MadsOpts(poll_vars === :xyr ? Int32(0) : poll_vars
                                        Int32(0), Int32(0), Int32(0))
 
 """
+MacMadsMesh — mac_mads_mesh (include/maxcover.h), 16 bytes: the native driver's per-variable granularity
+(DirectSearch's SetGranularity, src/TDM_STATIC_opt.jl:131-137): a pointer to 3N host doubles laid out as
+x (C_NULL: 1.0 everywhere), copied during the call, and a reserved word that is 0.
+"""
+struct MacMadsMesh
+    granularity::Ptr{Float64}
+    reserved::Int64
+end
+
+"The 3N granularities of `granularity`: a number, a pair (g_xy, g_r) or 3N numbers, each finite and > 0."
+function mesh_granularity(granularity, three_n::Integer)
+    N = three_n ÷ 3
+    g = granularity isa Real ? fill(Float64(granularity), three_n) :
+        length(granularity) == 2 ? vcat(fill(Float64(granularity[1]), 2N), fill(Float64(granularity[2]), three_n - 2N)) :
+        length(granularity) == three_n ? Vector{Float64}(collect(granularity)) :
+        throw(ArgumentError("granularity must be a number, a pair (g_xy, g_r) or $three_n numbers"))
+    all(v -> isfinite(v) && v > 0, g) || throw(ArgumentError("granularity: every entry must be finite and > 0"))
+    return g
+end
+
+"""
 mads_run(x0, r_max, ctx; prev, d_lim, tan_half_fov, n_iter, ell0, ell_max, seed, cons, poll_vars) — the whole
 granular-MADS loop inside libmaxcover (complete LTMADS poll generated on the device, cons3 as
 extreme barrier): the batched stand-in for TDM_STATIC_opt.optimize (src/TDM_STATIC_opt.jl:118-169).
@@ -421,23 +442,40 @@ evaluated; `nothing` keeps the plain call. `poll_vars = :xy` (mac_mads_run_opts,
 x and y only — 4N candidates per poll from a basis of size 2N, the radii of `x` equal to `x0`'s bit
 for bit — for the steps where "no height changes need to be explored" (src/TDM_STATIC_opt.jl:15-44);
 `:xyr`, the default, is the calls above. `motion::MacMotion` (mac_mads_run_motion) adds cons4 / cons5 /
-cons6 to every poll's mask. Like the rest of this shim, the `poll_vars` and `motion` paths have not been
-executed here. Returns (x, stats::MadsStats).
+cons6 to every poll's mask. `granularity` (mac_mads_run_mesh; `nothing`: the calls above): a number, a pair
+(g_xy, g_r) or 3N numbers laid out as `x0`; variable v then steps by g[v] times the basis's integers, as the
+reference's SetGranularity does (:131-137). Like the rest of this shim, the `poll_vars`, `motion` and
+`granularity` paths have not been executed here. Returns (x, stats::MadsStats).
 """
 function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                   penalty::Float64 = 1e5, prev::Union{Nothing,Vector{Float64}} = nothing,
                   d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
                   n_iter::Integer = 100, ell0::Integer = 2, ell_max::Integer = 6,
                   seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing,
-                  poll_vars::Symbol = :xyr, motion::Union{Nothing,MacMotion} = nothing)
+                  poll_vars::Symbol = :xyr, motion::Union{Nothing,MacMotion} = nothing,
+                  granularity = nothing)
     opts = MadsOpts(poll_vars)
+    g = granularity === nothing ? nothing : mesh_granularity(granularity, length(x0))
     x = similar(x0)
     prm = Ref(MadsParams(n_iter, ell0, ell_max, UInt64(seed)))
     st = Ref{MadsStats}()
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
-    GC.@preserve prev d_lim motion begin
-        if motion !== nothing
+    GC.@preserve prev d_lim motion g begin
+        if g !== nothing
+            rcons = cons === nothing ? nothing : Ref(cons)
+            rmot = motion === nothing ? nothing : Ref(CMotion(motion))
+            GC.@preserve rcons rmot begin
+                pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)
+                pmot = rmot === nothing ? Ptr{CMotion}(C_NULL) : Base.unsafe_convert(Ptr{CMotion}, rmot)
+                check(ccall((:mac_mads_run_mesh, libmaxcover), Int32,
+                            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                             Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats},
+                             Ptr{MacCons}, Ref{MadsOpts}, Ptr{CMotion}, Ref{MacMadsMesh}),
+                            ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st,
+                            pcons, Ref(opts), pmot, Ref(MacMadsMesh(pointer(g), 0))))
+            end
+        elseif motion !== nothing
             rcons = cons === nothing ? nothing : Ref(cons)
             GC.@preserve rcons begin
                 pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)

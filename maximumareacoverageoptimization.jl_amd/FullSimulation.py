@@ -26,7 +26,7 @@ import time
 
 import numpy as np
 
-from ._lib import Context, percentage_covered
+from ._lib import Context, mesh_granularity, percentage_covered
 from .DynamicArea import DynamicArea
 
 FOV = 100 / 180 * math.pi          # :735
@@ -62,13 +62,14 @@ def cons3_ok(prev: np.ndarray, x: np.ndarray, d_lim: np.ndarray) -> bool:
     return True
 
 
-def auto_poll_vars(R, r_max) -> str:
-    """The per-step choice of ``Simulation(poll_vars="auto")``: "xy" when every |R_i - r_max_i| <= 0.5
-    at the MADS input — no +-1 step of a radius on the granular mesh then lowers the objective's
-    1e5 |R_i - r_max_i| (src/TDM_STATIC_opt.jl:92), the reference CustomPoll's "height constraint is
-    already being satisfied" (:15-44) — else "xyr". Needs no GPU."""
+def auto_poll_vars(R, r_max, g_r=1.0) -> str:
+    """The per-step choice of ``Simulation(poll_vars="auto")``: "xy" when every |R_i - r_max_i| <=
+    g_r_i / 2 (0.5 on the unit mesh) at the MADS input — no step of a radius by its granularity
+    ``g_r`` (a scalar or N values) then lowers the objective's 1e5 |R_i - r_max_i|
+    (src/TDM_STATIC_opt.jl:92), the reference CustomPoll's "height constraint is already being
+    satisfied" (:15-44) — else "xyr". Needs no GPU."""
     d = np.abs(np.asarray(R, dtype=np.float64) - np.asarray(r_max, dtype=np.float64))
-    return "xy" if bool(np.all(d <= 0.5)) else "xyr"
+    return "xy" if bool(np.all(d <= np.asarray(g_r, dtype=np.float64) / 2)) else "xyr"
 
 
 def split_cons_ext(cons_ext):
@@ -146,17 +147,21 @@ class Simulation:
     switches on cons4 / cons5 / cons6 (include/maxcover.h mac_motion) from t >= 3 on, around the
     previous MADS output (derive_motion); ``velocities``: a callable t -> [vx; vy] for cons4, None:
     the last target move (perfect tracking). Every rank derives the same arrays in all three modes;
-    with ``motion=None`` the records and calls are what they were."""
+    with ``motion=None`` the records and calls are what they were.
+    ``granularity``: the MADS mesh of every step (None, a scalar, a pair (g_xy, g_r) or 3N values:
+    Context.mads_run, mac_mads_mesh), in all three modes; "auto" then compares with g_r / 2. None:
+    the calls as they were."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
                  shard=None, gather=None, speculate: bool | None = None, device=None,
                  attribution: bool = False, cons_ext=(), high_interest=None, w_high=None,
-                 poll_vars: str = "xyr", motion=None, velocities=None):
+                 poll_vars: str = "xyr", motion=None, velocities=None, granularity=None):
         if poll_vars not in ("xyr", "xy", "auto"):
             raise ValueError(f"poll_vars must be 'xyr', 'xy' or 'auto', not {poll_vars!r}")
         self.poll_vars = poll_vars
+        self.granularity = mesh_granularity(granularity, np.asarray(starting_circles).size)
         self.ctx = ctx
         self.high_interest = self._boxes(high_interest)
         if self.high_interest is None and w_high is not None:
@@ -274,9 +279,12 @@ class Simulation:
             kw["motion"] = mo
         pvars = self.poll_vars
         if pvars == "auto":
-            pvars = auto_poll_vars(single_input[2 * N:], self.r_max)
+            pvars = auto_poll_vars(single_input[2 * N:], self.r_max,
+                                   1.0 if self.granularity is None else self.granularity[2 * N:])
         if pvars != "xyr":   # (the default: the calls as they were)
             kw["poll_vars"] = pvars
+        if self.granularity is not None:
+            kw["granularity"] = self.granularity
         if self.shard is None or self.shard[1] == 1:
             x_out, st = ctx.mads_run(single_input, self.r_max, 1e5, **kw)
         elif self.speculate:

@@ -17,7 +17,7 @@ import time
 
 import numpy as np
 
-from ._lib import Context, InexactError, default_context
+from ._lib import Context, InexactError, default_context, mesh_granularity
 from .TDM_Constraints import merge_mac_cons, merge_mac_motion
 from .workloads import SplitMix64, ltmads_basis
 
@@ -120,8 +120,14 @@ def poll_matrix(x: np.ndarray, B: np.ndarray) -> np.ndarray:
     return X
 
 
+def scaled_basis(B: np.ndarray, g) -> np.ndarray:
+    """B with row v scaled by the granularity g[v] of polled variable v (one product per entry, the
+    native driver's fl(g[v] * L); g None: B as it is)."""
+    return B if g is None else g[:B.shape[0], None] * B
+
+
 def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-         seed: int = 20250216, poll_vars: str = "xyr") -> MADSResult:
+         seed: int = 20250216, poll_vars: str = "xyr", granularity=None) -> MADSResult:
     """Granular MADS, complete poll over D = [B, -B] (B an LTMADS-style integer basis whose
     entries are bounded by 2^ell), extreme barrier on cons_ext. Success: ell <- min(ell+1,
     ell_max) (larger steps); failure: ell <- ell-1; stop when ell < 0 (below the granularity
@@ -131,11 +137,15 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
     create_cons6) are applied on the device inside the poll; the
     iterates are the ones the same constraints give as plain host callables.
     ``poll_vars="xy"``: the basis is drawn over the n_p = 2N variables x, y (same stream, n := n_p)
-    and the radii are held (MAC_POLL_XY, include/maxcover.h)."""
+    and the radii are held (MAC_POLL_XY, include/maxcover.h).
+    ``granularity``: DirectSearch's SetGranularity (src/TDM_STATIC_opt.jl:131-137) per variable: None,
+    a scalar, a pair (g_xy, g_r) or 3N values laid out as x; variable v steps by g[v] times the
+    basis's integers (mac_mads_mesh, include/maxcover.h). None is 1.0 everywhere."""
     t0 = time.perf_counter()
     res = MADSResult()
     x = np.asarray(input, dtype=np.float64).copy()
     n = polled_count(x.size, poll_vars)
+    g = mesh_granularity(granularity, x.size)
     rng = SplitMix64(seed)
     cons = list(cons_ext)
 
@@ -156,7 +166,7 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
     it = 0
     while it < N_iter and ell >= 0:
         it += 1
-        B = ltmads_basis(n, ell, rng).astype(np.float64)
+        B = scaled_basis(ltmads_basis(n, ell, rng).astype(np.float64), g)
         X = poll_matrix(x, B)
         n3 = sum(bool(cons3(v)) for v in X) if cons3 is not None else X.shape[0]
         res.status.cons3_passed += n3
@@ -204,13 +214,15 @@ class PollStepper:
     driven by ``dist.mads_loop``: the poll sequence of ``mads`` (same stream, same update rule),
     of which this stepper evaluates only the shard [lo, hi) of every poll's 2n candidates, through
     ``poll_fn(X_shard) -> (best_obj, best_local_index)`` (index -1: nothing feasible). Every rank
-    draws the whole basis, so all ranks stay at the same stream position. ``poll_vars``: as
-    ``mads`` (n = n_p, the polled variables)."""
+    draws the whole basis, so all ranks stay at the same stream position. ``poll_vars`` and
+    ``granularity``: as ``mads`` (n = n_p, the polled variables)."""
 
     def __init__(self, x0, f0: float, poll_fn, N_iter: int = 100, ell0: int = 2,
-                 ell_max: int = 6, seed: int = 20250216, shard=None, poll_vars: str = "xyr"):
+                 ell_max: int = 6, seed: int = 20250216, shard=None, poll_vars: str = "xyr",
+                 granularity=None):
         self.x = np.asarray(x0, dtype=np.float64).copy()
         self.n = polled_count(self.x.size, poll_vars)
+        self.g = mesh_granularity(granularity, self.x.size)
         self.f = float(f0)
         self.poll_fn = poll_fn
         self.N_iter, self.ell, self.ell_max = N_iter, ell0, ell_max
@@ -224,7 +236,7 @@ class PollStepper:
         if self.it >= self.N_iter or self.ell < 0:
             return True, np.inf, -1
         self.it += 1
-        B = ltmads_basis(self.n, self.ell, self.rng).astype(np.float64)
+        B = scaled_basis(ltmads_basis(self.n, self.ell, self.rng).astype(np.float64), self.g)
         self._X = poll_matrix(self.x, B)
         Xs = self._X[self.lo:self.hi]
         if Xs.shape[0] == 0:
@@ -250,7 +262,7 @@ class PollStepper:
         rng = SplitMix64()
         with np.errstate(over="ignore"):
             rng.state = self.rng.state + np.uint64(ahead * self._draws()) * np.uint64(0x9E3779B97F4A7C15)
-        B = ltmads_basis(self.n, self.ell - ahead, rng).astype(np.float64)
+        B = scaled_basis(ltmads_basis(self.n, self.ell - ahead, rng).astype(np.float64), self.g)
         return poll_matrix(self.x, B)
 
     def poll_ahead(self, ahead: int):

@@ -78,6 +78,7 @@ EXPORTS = (
     "mac_mads_run_opts", "mac_mads_begin_opts",
     "mac_cons_mask_motion_f64", "mac_poll_best_motion_f64", "mac_motion_thresholds",
     "mac_mads_run_motion", "mac_mads_begin_motion",
+    "mac_mads_run_mesh", "mac_mads_begin_mesh", "mac_profile_fused",
 )
 
 MAC_REGIONS_MAX = 64
@@ -137,6 +138,36 @@ def poll_vars_code(poll_vars) -> int:
         return POLL_VARS[poll_vars]
     except (KeyError, TypeError):
         raise ValueError(f"poll_vars must be 'xyr' or 'xy', not {poll_vars!r}") from None
+
+
+class MadsMesh(ctypes.Structure):
+    """mac_mads_mesh (include/maxcover.h): the native driver's per-variable granularity (16 B,
+    reserved = 0). ``granularity``: 3N host doubles laid out as x, or null for 1.0 everywhere."""
+    _fields_ = [("granularity", ctypes.POINTER(ctypes.c_double)), ("reserved", ctypes.c_int64)]
+
+
+def mesh_granularity(granularity, three_n: int):
+    """The granularity vector g of a MADS run over ``three_n`` variables (x_0.., y_0.., r_0..), or
+    None (1.0 everywhere): ``granularity`` is None, a scalar, a pair (g_xy, g_r) or ``three_n``
+    values. Every entry must be finite and > 0 (ValueError otherwise)."""
+    if granularity is None:
+        return None
+    try:
+        g = np.asarray(granularity, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"granularity must be a number, a pair (g_xy, g_r) or {three_n} numbers, "
+                         f"not {granularity!r}") from None
+    N = three_n // 3
+    if g.ndim == 0:
+        g = np.full(three_n, float(g))
+    elif g.ndim == 1 and g.size == 2:
+        g = np.concatenate([np.full(2 * N, g[0]), np.full(three_n - 2 * N, g[1])])
+    elif g.ndim != 1 or g.size != three_n:
+        raise ValueError(f"granularity must be a number, a pair (g_xy, g_r) or {three_n} numbers, "
+                         f"not an array of shape {g.shape}")
+    if not (np.isfinite(g).all() and (g > 0).all()):
+        raise ValueError("granularity: every entry must be finite and > 0")
+    return np.ascontiguousarray(g, dtype=np.float64)
 
 
 class FireParams(ctypes.Structure):
@@ -301,6 +332,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_profile_read": ([_vp, _dp, _i64p, _i64p, ctypes.POINTER(_i32), _i32], _i32),
         "mac_profile_split": ([_vp, _dp, _dp, _dp, _i64p], _i32),
         "mac_profile_kernels": ([_vp, _dp, _i64p, _i32], _i32),
+        "mac_profile_fused": ([_vp, _i64p, _i64p, _i64p, _i32], _i32),
         "mac_append_points_f64": ([_vp, _dp, _dp, _dp, _i64], _i32),
         "mac_mads_run": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                           ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats)], _i32),
@@ -330,6 +362,14 @@ def _declare(L: ctypes.CDLL) -> None:
                                    ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
                                    ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
                                    ctypes.POINTER(Motion)], _i32),
+        "mac_mads_run_mesh": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                               ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats),
+                               ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
+                               ctypes.POINTER(Motion), ctypes.POINTER(MadsMesh)], _i32),
+        "mac_mads_begin_mesh": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                                 ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
+                                 ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
+                                 ctypes.POINTER(Motion), ctypes.POINTER(MadsMesh)], _i32),
         "mac_append_points_dev_f64": ([_vp, _vp, _vp, _vp, _i64], _i32),
         "mac_fire_last_error": ([], ctypes.c_char_p),
         "mac_fire_thresholds": ([ctypes.POINTER(FireParams), _dp], None),
@@ -572,6 +612,15 @@ class Context:
         cnt = (ctypes.c_int64 * n)()
         _check(self._L.mac_profile_kernels(self._h, ms, cnt, n))
         return {name: (ms[r], int(cnt[r])) for r, name in enumerate(PROF_ROLES)}
+
+    def profile_fused(self, reset: bool = False) -> dict:
+        """With profiling on, the fused chain's hint reports read so far (mac_profile_fused): reports,
+        and the sum and the largest of hint word 1 (disks of a poll that took one position per
+        candidate)."""
+        r, s, m = _i64(), _i64(), _i64()
+        _check(self._L.mac_profile_fused(self._h, ctypes.byref(r), ctypes.byref(s), ctypes.byref(m),
+                                         1 if reset else 0))
+        return {"reports": int(r.value), "ident_sum": int(s.value), "ident_max": int(m.value)}
 
     # -- point list
     def set_points(self, x, y, w) -> None:
@@ -896,16 +945,20 @@ class Context:
     # -- native MADS driver
     def mads_run(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                  tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-                 seed: int = 20250216, cons=None, poll_vars: str = "xyr", motion=None):
+                 seed: int = 20250216, cons=None, poll_vars: str = "xyr", motion=None,
+                 granularity=None):
         """mac_mads_run: the whole MADS loop in libmaxcover (candidates generated on the device).
         ``cons`` (a Cons, or anything make_cons takes, e.g. TDM_Constraints.merge_mac_cons's
         mapping): the swarm constraints every poll applies on the device (mac_mads_run_cons); None
         keeps the plain call. ``poll_vars``: "xyr" polls every variable (the calls above), "xy"
         x and y only with the radii held (mac_mads_run_opts, MAC_POLL_XY). ``motion`` (a Motion, or
         anything make_motion takes): the target-motion constraints on every poll
-        (mac_mads_run_motion). Returns (x, stats dict)."""
+        (mac_mads_run_motion). ``granularity``: None, a scalar, a pair (g_xy, g_r) or 3N values laid
+        out as x0 (mesh_granularity): variable v steps by g[v] times the basis's integers
+        (mac_mads_run_mesh); None keeps the calls above. Returns (x, stats dict)."""
         pvars = poll_vars_code(poll_vars)
         x = _f64(x0)
+        g = mesh_granularity(granularity, x.size)
         rm = _f64(r_max)
         pv = _f64(prev) if prev is not None else None
         dl = _f64(d_lim) if d_lim is not None else None
@@ -916,7 +969,12 @@ class Context:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), _ptr(out), ctypes.byref(st))
         cs = make_cons(cons)
-        if motion is not None:
+        if g is not None:
+            op, mo = MadsOpts(pvars), make_motion(motion) if motion is not None else None
+            mesh = MadsMesh(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 0)
+            _check(self._L.mac_mads_run_mesh(*args, _opt(cs), ctypes.byref(op), _opt(mo),
+                                             ctypes.byref(mesh)))
+        elif motion is not None:
             op, mo = MadsOpts(pvars), make_motion(motion)
             _check(self._L.mac_mads_run_motion(*args, _opt(cs), ctypes.byref(op), _opt(mo)))
         elif pvars != MAC_POLL_XYR:
@@ -932,14 +990,16 @@ class Context:
     def mads_stepper(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                      tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2,
                      ell_max: int = 6, seed: int = 20250216, shard=None,
-                     cons=None, poll_vars: str = "xyr", motion=None) -> "MadsStepper":
+                     cons=None, poll_vars: str = "xyr", motion=None,
+                     granularity=None) -> "MadsStepper":
         """mac_mads_begin: the native loop one poll at a time over the candidate shard
         ``shard`` = (lo, hi) of each poll's 2 n_p candidates (None: the whole poll). ``cons``: as
         mads_run's (mac_mads_begin_cons; every rank of a sharded loop passes the same one).
         ``poll_vars``: as mads_run's (n_p = 3N for "xyr", 2N for "xy": mac_mads_begin_opts).
-        ``motion``: as mads_run's (mac_mads_begin_motion; the same on every rank)."""
+        ``motion``: as mads_run's (mac_mads_begin_motion; the same on every rank).
+        ``granularity``: as mads_run's (mac_mads_begin_mesh; the same on every rank)."""
         st = MadsStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
-                         ell_max, seed, shard, cons, poll_vars, motion)
+                         ell_max, seed, shard, cons, poll_vars, motion, granularity)
         self._steppers.add(st)
         return st
 
@@ -1140,11 +1200,13 @@ class MadsStepper:
     (0, candidates)."""
 
     def __init__(self, ctx: Context, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter,
-                 ell0, ell_max, seed, shard, cons=None, poll_vars: str = "xyr", motion=None):
+                 ell0, ell_max, seed, shard, cons=None, poll_vars: str = "xyr", motion=None,
+                 granularity=None):
         pvars = poll_vars_code(poll_vars)
+        x = _f64(x0)
+        g = mesh_granularity(granularity, x.size)   # (validated before the library is touched)
         self._L = ctx._L
         self._ctx = ctx   # keeps the context alive while the stepper lives
-        x = _f64(x0)
         rm = _f64(r_max)
         pv = _f64(prev) if prev is not None else None
         dl = _f64(d_lim) if d_lim is not None else None
@@ -1160,7 +1222,12 @@ class MadsStepper:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), lo, hi, ctypes.byref(h))
         cs = make_cons(cons)
-        if motion is not None:
+        if g is not None:   # (the library copies the vector during the call)
+            op, mo = MadsOpts(pvars), make_motion(motion) if motion is not None else None
+            mesh = MadsMesh(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 0)
+            _check(self._L.mac_mads_begin_mesh(*args, _opt(cs), ctypes.byref(op), _opt(mo),
+                                               ctypes.byref(mesh)))
+        elif motion is not None:
             op, mo = MadsOpts(pvars), make_motion(motion)
             _check(self._L.mac_mads_begin_motion(*args, _opt(cs), ctypes.byref(op), _opt(mo)))
         elif pvars != MAC_POLL_XYR:

@@ -85,8 +85,9 @@ __host__ __device__ __forceinline__ uint64_t mirror_check(uint64_t o, uint64_t i
 // is refined), with the same ltmads_entry values and per-variable adds, so the pipelined loop visits
 // the stepper's incumbents bit for bit. ell, f: the state before the poll.
 // kXY: an xy-only poll (fb.np polled variables; selected at compile time, so the full poll's
-// finalize is the code it was).
-template <bool kXY = false>
+// finalize is the code it was). kMesh: the loop runs on a mesh (the state's gran: the step is
+// CandSrc.step_m's product), likewise selected at compile time.
+template <bool kXY = false, bool kMesh = false>
 __device__ __forceinline__ void mads_step(const FinBest& fb, double bo, int64_t gidx, int ell, double f)
 {
     const int lane = threadIdx.x & (kWave - 1);
@@ -101,21 +102,26 @@ __device__ __forceinline__ void mads_step(const FinBest& fb, double bo, int64_t 
     const int64_t b = (int64_t)1 << ell;
     const bool plus = gidx < np;
     const int c = better ? fb.cp[plus ? (int)gidx : (int)gidx - np] : 0;
+    [[maybe_unused]] const double* gran = nullptr;
+    if constexpr (kMesh) gran = fb.st->gran;
     for (int v0 = lane; v0 < n; v0 += kB * kWave) {
         double xv[kB];
+        [[maybe_unused]] double gv[kB];
         int rv[kB];
 #pragma unroll
         for (int j = 0; j < kB; ++j) {
             const int v = v0 + j * kWave;
             xv[j] = v < n ? x[v] : 0.0;
             rv[j] = better && v < np ? fb.rp[v] : 0;
+            if constexpr (kMesh) gv[j] = better && v < np ? gran[v] : 1.0;
         }
 #pragma unroll
         for (int j = 0; j < kB; ++j) {
             const int v = v0 + j * kWave;
             if (v >= n) break;
             if (better) {   // (a held variable, v >= np: x's double as it is, by a select)
-                const double d = ltmads_entry(fb.state, np, b, rv[j], c);
+                double d = ltmads_entry(fb.state, np, b, rv[j], c);
+                if constexpr (kMesh) d = gv[j] * d;   // the mesh: CandSrc.step_m's product
                 const double moved = plus ? xv[j] + d : xv[j] - d;
                 xn[v] = v < np ? moved : xv[j];
             } else {
@@ -147,7 +153,7 @@ __device__ __forceinline__ void argmin_take(double& v1, int& i1, double v2, int 
 // loads every minimum with sc1 loads, in the same wave. The lexicographic (objective, index)
 // minimum is order-independent (the sequential first-best order); NaN / +inf never selected.
 // C: lanes holding the block's candidates (a power of two <= 64). Returns true in the last block.
-template <int C = kFinC, bool kXY = false>
+template <int C = kFinC, bool kXY = false, bool kMesh = false>   // (kMesh: mads_step's)
 __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int k, bool have)
 {
     static_assert(C >= 1 && C <= kWave && (C & (C - 1)) == 0, "C: a power of two up to a wave");
@@ -214,7 +220,7 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
         return true;
     }
     if (fb.st) {
-        mads_step<kXY>(fb, bo, gidx, ell, fcur);
+        mads_step<kXY, kMesh>(fb, bo, gidx, ell, fcur);
         if (rej && lane == 0) fb.st->skipped += 1;
     }
     if (lane == 0) {
@@ -249,7 +255,8 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
     return true;
 }
 
-template <bool kXY = false>   // (kXY: the pipelined loop's update of an xy-only poll, mads_step)
+// (kXY: the pipelined loop's update of an xy-only poll, mads_step; kMesh: ... on a mesh)
+template <bool kXY = false, bool kMesh = false>
 __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
     const double* __restrict__ partial, const int* __restrict__ mode, int n_poll, int n_other,
     int K, int N, const int* __restrict__ map, const double* __restrict__ spart,
@@ -339,7 +346,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
                 if (vp) o = -area + vpk;
                 if (obj_out) obj_out[k] = o;
             }
-            if (fb.best && t < kWave) finalize_argmin<kFinC, kXY>(fb, o, k, k < K);
+            if (fb.best && t < kWave) finalize_argmin<kFinC, kXY, kMesh>(fb, o, k, k < K);
             ts_end(ts);
             return;
         }
@@ -384,7 +391,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
         if (vp) o = -area + vpk;
         if (obj_out) obj_out[k] = o;
     }
-    if (fb.best && t < kWave) finalize_argmin<kFinC, kXY>(fb, o, k, k < K);
+    if (fb.best && t < kWave) finalize_argmin<kFinC, kXY, kMesh>(fb, o, k, k < K);
     ts_end(ts);
 }
 

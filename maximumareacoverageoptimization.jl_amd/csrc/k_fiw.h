@@ -152,20 +152,21 @@ __device__ __forceinline__ DiskRec word_disk(uint32_t w, double bx, double by, d
 // built once per source: a run-time choice at each call site inlines the whole LTMADS / basis-form
 // generator there and keeps its operands in scalar registers through code a matrix poll never runs
 // (DESIGN.md §4 "Two instantiations per source").
-template <bool kMat>
+// kMesh: a generated poll on a mesh (mac_mads_mesh), likewise known at the enqueue and its own build.
+template <bool kMat, bool kMesh = false>
 __device__ __forceinline__ double src_val(const CandSrc& s, int k, int v, int N)
 {
-    return s.val<kMat>(k, v, N);
+    return s.val<kMat, kMesh>(k, v, N);
 }
 
 // Disk jj of candidate k from its key word, or the candidate's own values when the key escaped
-template <bool kMat>
+template <bool kMat, bool kMesh = false>
 __device__ __forceinline__ DiskRec key_disk(const CandSrc& s, uint32_t key, int jj, int k, int N, double bx,
                                             double by, double br)
 {
     if (key != kKeyEsc) return word_disk(key, bx, by, br);
-    return make_disk(src_val<kMat>(s, k, jj, N), src_val<kMat>(s, k, N + jj, N),
-                     src_val<kMat>(s, k, 2 * N + jj, N));
+    return make_disk(src_val<kMat, kMesh>(s, k, jj, N), src_val<kMat, kMesh>(s, k, N + jj, N),
+                     src_val<kMat, kMesh>(s, k, 2 * N + jj, N));
 }
 
 #ifdef MAC_DIAG
@@ -194,7 +195,7 @@ template <> struct FwAcc<true> { typedef unsigned T; };
 
 // kCounts == (a.counts != 0): the equal-weight build keeps its credits in 32-bit integers (half the
 // registers of the walk's accumulators and of the shared credits)
-template <bool kCounts, bool kMat>
+template <bool kCounts, bool kMat, bool kMesh = false>   // (kMesh: generated polls only)
 __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2))) void fiw_kernel(
     uint64_t* ts, FwArgs a)
 {
@@ -286,8 +287,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         }
         pq[kFwPer] = tid == 0 && K > kFwMaxK ? krow[kFwMaxK] : 0u;
         dj[kFwPer] = tid == 0 && K > kFwMaxK && a.dead && a.dead[kFwMaxK] != 0;
-        const double bx = src_val<kMat>(src, 0, i, N), by = src_val<kMat>(src, 0, N + i, N),
-                     br = src_val<kMat>(src, 0, 2 * N + i, N);
+        const double bx = src_val<kMat, kMesh>(src, 0, i, N), by = src_val<kMat, kMesh>(src, 0, N + i, N),
+                     br = src_val<kMat, kMesh>(src, 0, 2 * N + i, N);
         double dmx = -__builtin_inf(), dmy = -__builtin_inf(), dmr = -__builtin_inf(), dml = -__builtin_inf();
         for (int q = tid; q < a.npd; q += kFwThreads) {
             const double4 d4 = a.pd[q];
@@ -301,9 +302,9 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         for (int q = 0; q < 2; ++q) {
             const int j = tid + q * kFwThreads;
             const int jc = min(j, N - 1);
-            jb[q][0] = j < i ? src_val<kMat>(src, 0, jc, N) : 0.0;
-            jb[q][1] = j < i ? src_val<kMat>(src, 0, N + jc, N) : 0.0;
-            jb[q][2] = j < i ? src_val<kMat>(src, 0, 2 * N + jc, N) : 0.0;
+            jb[q][0] = j < i ? src_val<kMat, kMesh>(src, 0, jc, N) : 0.0;
+            jb[q][1] = j < i ? src_val<kMat, kMesh>(src, 0, N + jc, N) : 0.0;
+            jb[q][2] = j < i ? src_val<kMat, kMesh>(src, 0, 2 * N + jc, N) : 0.0;
         }
         if (tid == 0) {
             ucnt = 0;
@@ -385,8 +386,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
                 if (j < i) test(j, jb[q][0], jb[q][1], jb[q][2]);
             }
             for (int j = tid + 2 * kFwThreads; j < i; j += kFwThreads)
-                test(j, src_val<kMat>(src, 0, j, N), src_val<kMat>(src, 0, N + j, N),
-                     src_val<kMat>(src, 0, 2 * N + j, N));
+                test(j, src_val<kMat, kMesh>(src, 0, j, N), src_val<kMat, kMesh>(src, 0, N + j, N),
+                     src_val<kMat, kMesh>(src, 0, 2 * N + j, N));
         }
         MAC_FW_STAMP(12);
         // ---- positions. Direct-mapped when the live candidates' key offsets fit a small box
@@ -568,8 +569,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
     auto pos_disk = [&](int u) -> DiskRec {
         if (ident) {
             if (cinfo[u] & 0x8000) return inert_disk();
-            return make_disk(src_val<kMat>(src, u, i, N), src_val<kMat>(src, u, N + i, N),
-                             src_val<kMat>(src, u, 2 * N + i, N));
+            return make_disk(src_val<kMat, kMesh>(src, u, i, N), src_val<kMat, kMesh>(src, u, N + i, N),
+                             src_val<kMat, kMesh>(src, u, 2 * N + i, N));
         }
         return word_disk(poskey[u], sbase[0], sbase[1], sbase[2]);
     };
@@ -583,9 +584,9 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         DiskRec d;
         if (ident) {
             if (cinfo[u] & 0x8000) return inert_disk();
-            d.cx = src_val<kMat>(src, u, i, N);
-            d.cy = src_val<kMat>(src, u, N + i, N);
-            d.r = src_val<kMat>(src, u, 2 * N + i, N);
+            d.cx = src_val<kMat, kMesh>(src, u, i, N);
+            d.cy = src_val<kMat, kMesh>(src, u, N + i, N);
+            d.r = src_val<kMat, kMesh>(src, u, 2 * N + i, N);
         } else {
             const uint32_t w = poskey[u];
             if (w == kDeadWord) return inert_disk();
@@ -1003,7 +1004,7 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
                             for (int j = 0; j < P; ++j) {
                                 if (!Mj[j]) continue;
-                                const DiskRec d = key_disk<kMat>(src, key[j], jj, kof(j), N, x0, y0, r0);
+                                const DiskRec d = key_disk<kMat, kMesh>(src, key[j], jj, kof(j), N, x0, y0, r0);
                                 for (uint64_t b = Mj[j]; b;) {
                                     const int e = __builtin_ctzll(b);
                                     b &= b - 1;
@@ -1015,8 +1016,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
                             for (int m = 0; m < nclist; ++m) strip(nb_id[m], nb_b[m][0], nb_b[m][1], nb_b[m][2]);
                         } else {   // overflowed list: every lower disk whose box overlaps box i
                             for (int jj = 0; jj < i; ++jj) {
-                                const double x0 = src_val<kMat>(src, 0, jj, N), y0 = src_val<kMat>(src, 0, N + jj, N),
-                                             r0 = src_val<kMat>(src, 0, 2 * N + jj, N);
+                                const double x0 = src_val<kMat, kMesh>(src, 0, jj, N), y0 = src_val<kMat, kMesh>(src, 0, N + jj, N),
+                                             r0 = src_val<kMat, kMesh>(src, 0, 2 * N + jj, N);
                                 int4 B;
                                 if (sup_box(x0, y0, r0, sbase[3], sbase[4], sbase[5], g, B) && box_overlap(B, RG))
                                     strip(jj, x0, y0, r0);
@@ -1134,7 +1135,7 @@ struct F2Shared {
     const uint8_t* dead;
 };
 
-template <bool kCounts, bool kMat, bool kXY = false>   // (kXY: as finalize_kernel's; generated polls only)
+template <bool kCounts, bool kMat, bool kXY = false, bool kMesh = false>   // (kXY, kMesh: as finalize_kernel's; generated polls only)
 __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     const unsigned* __restrict__ crow, const double* __restrict__ frow, int ldk, int N, int K,
     double w0, const double* __restrict__ vp, double* __restrict__ area_out, double* __restrict__ obj_out,
@@ -1150,7 +1151,7 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     const int k = cb * C + c;
     const int kc = min(k, K - 1);
     CandSrc src = sd.src;
-    static_assert(!(kMat && kXY), "xy-only polls are generated");
+    static_assert(!(kMat && (kXY || kMesh)), "xy-only polls and meshes are generated");
     const bool run = src.resolve_as<kMat>();   // (a stopped pipelined MADS loop: nothing to add)
     __shared__ double fred[G][C];
     __shared__ uint64_t ired[G][C];
@@ -1360,13 +1361,13 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
             const bool rec = sl < ns;
             const int jj = sdisk[rec ? sl : 0];
             const uint32_t key = src.keysP[(int64_t)jj * src.ldk + kc];
-            const double bx = src_val<kMat>(src, 0, jj, N), by = src_val<kMat>(src, 0, N + jj, N),
-                         br = src_val<kMat>(src, 0, 2 * N + jj, N);
+            const double bx = src_val<kMat, kMesh>(src, 0, jj, N), by = src_val<kMat, kMesh>(src, 0, N + jj, N),
+                         br = src_val<kMat, kMesh>(src, 0, 2 * N + jj, N);
             int e0 = e0all, ne = min(kF2Ent, e1all - e0);
             stage(q0, q1, sl0, e0, ne);
             if constexpr (decltype(first)::value) sum_rows();
             if (rec) {
-                const DiskRec d = key_disk<kMat>(src, key, jj, kc, N, bx, by, br);
+                const DiskRec d = key_disk<kMat, kMesh>(src, key, jj, kc, N, bx, by, br);
                 srec[sl][0][c] = d.cx;
                 srec[sl][1][c] = d.cy;
                 srec[sl][2][c] = d.T;
@@ -1510,7 +1511,7 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     }
     MAC_F2_STAMP(4);
     if (fb.best && t < kWave) {
-        [[maybe_unused]] const bool last = finalize_argmin<C, kXY>(fb, o, k, k < K);   // (+ the hint words)
+        [[maybe_unused]] const bool last = finalize_argmin<C, kXY, kMesh>(fb, o, k, k < K);   // (+ the hint words)
 #ifdef MAC_DIAG
         if (t == 0 && blockIdx.x < 4096) g_diag_f2[8 * blockIdx.x + 7] = last;
 #endif

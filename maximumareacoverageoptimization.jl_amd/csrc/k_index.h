@@ -135,11 +135,13 @@ __device__ __forceinline__ float key_of(double v, double b, bool& ok)
 // disk).
 // kXY: an xy-only generated poll (src.np != 0), selected at compile time: the full poll's
 // instantiation is the code it was.
-template <bool kKeys, int kPer, bool kXY = false>
+// kMesh: a generated poll on a mesh (mac_mads_mesh; CandSrc.step_m), likewise its own build.
+template <bool kKeys, int kPer, bool kXY = false, bool kMesh = false>
 __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPer <= 3 ? 8 : 4))) void disk_index_kernel(
     uint64_t* ts, CandSrc src0, int N, int K, Grid g, int dedup, IndexOut o)
 {
     CandSrc src = src0;
+    constexpr int kM = kMesh ? CandSrc::kOnMesh : CandSrc::kNoMesh;
     constexpr int kIdxPer = kPer;
     constexpr int kIndexMaxK = IdxShape<kPer>::MaxK;
     constexpr int kIndexSlots = IdxShape<kPer>::Slots;
@@ -212,9 +214,9 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
             y = c[N + i];
             r = c[2 * N + i];
         } else {
-            x = kXY ? src.get(k, i, N) : src.get_full(k, i, N);
-            y = kXY ? src.get(k, N + i, N) : src.get_full(k, N + i, N);
-            r = kXY ? src.get(k, 2 * N + i, N) : src.get_full(k, 2 * N + i, N);
+            x = kXY ? src.get_m<kM>(k, i, N) : src.get_full_m<kM>(k, i, N);
+            y = kXY ? src.get_m<kM>(k, N + i, N) : src.get_full_m<kM>(k, N + i, N);
+            r = kXY ? src.get_m<kM>(k, 2 * N + i, N) : src.get_full_m<kM>(k, 2 * N + i, N);
         }
     };
 
@@ -296,7 +298,15 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
                                    : (int16_t)ltmads_entry(src.state, n, src.b, r, c);
             }
             __syncthreads();
+            // (a mesh, mac_mads_mesh: one scale per axis, the granularity of disk i's x, y and r)
             const double sc = src.ltri ? src.delta : 1.0;
+            double scx = sc, scy = sc, scr = sc;
+            if constexpr (kMesh) {
+                const double* const gm = src.mesh();
+                scx = gm[i];
+                scy = gm[N + i];
+                scr = gm[2 * N + i];
+            }
             const double xi = src.xinc[i], yi = src.xinc[N + i], ri = src.xinc[2 * N + i];
 #pragma unroll
             for (int j = 0; j < P; ++j) {
@@ -304,8 +314,8 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
                 const int kg = kl + src.k0;
                 const bool plus = kg < n;
                 const int kk = plus ? kg : kg - n;
-                const double dx = sc * (double)dtab[kk], dy = sc * (double)dtab[n + kk],
-                             dr = sc * (double)dtab[2 * n + kk];
+                const double dx = scx * (double)dtab[kk], dy = scy * (double)dtab[n + kk],
+                             dr = scr * (double)dtab[2 * n + kk];
                 cx[j] = plus ? xi + dx : xi - dx;
                 cy[j] = plus ? yi + dy : yi - dy;
                 cr[j] = plus ? ri + dr : ri - dr;

@@ -122,6 +122,7 @@ struct MadsState {
     unsigned long long feas;   // candidates evaluated (passing cons3)
     int64_t skipped;           // polls rejected whole
     int64_t succ;              // successful polls (the incumbent moved)
+    const double* gran;        // the mesh's granularity per variable (CandSrc.mesh below; null: none)
 };
 
 // Where candidate coordinates come from: a 3N x K column-major matrix (the batch APIs), or a
@@ -149,6 +150,11 @@ struct CandSrc {
     // mesh size delta, src/TDM_STATIC_opt.jl:22-44): L's lower triangle packed by rows (int16,
     // entry (r, c <= r) at r(r+1)/2 + c) and B's entries delta * L instead of the stream's draws
     // (null: the stream). b is then a bound on |L| (the index's int16 table) and delta scales it.
+    // On the stream (ltri null) delta's eight bytes hold the native MADS driver's mesh instead
+    // (mac_mads_mesh; set_mesh / mesh below): the device pointer to the granularity g of every
+    // variable (3N doubles; null, delta's 0.0: 1.0 everywhere, the draws as they are). Variable v's
+    // step is fl(g[v] * entry): one product (step below). One slot for both, so the launches'
+    // arguments keep their size (a larger CandSrc costs prep_x_kernel's matrix build two spills).
     const int16_t* ltri;
     double delta;
     // (host only) the chain a generated poll takes under MAC_CHAIN_AUTO: 1 = the five-launch chain
@@ -173,18 +179,51 @@ struct CandSrc {
         if (ltri) return r < c ? 0.0 : delta * (double)ltri[(int64_t)r * (r + 1) / 2 + c];
         return ltmads_entry(state, n, b, r, c);
     }
+    // (through an integer: a cast of the double's bits straight to a pointer went through the stack)
+    __host__ __device__ __forceinline__ const double* mesh_ptr() const
+    {
+        return reinterpret_cast<const double*>(__builtin_bit_cast(uint64_t, delta));
+    }
+    __host__ __device__ __forceinline__ const double* mesh() const { return ltri ? nullptr : mesh_ptr(); }
+    __host__ void set_mesh(const double* g)   // (ltri null)
+    {
+        delta = __builtin_bit_cast(double, reinterpret_cast<uint64_t>(g));
+    }
+    // Polled variable v's step of B's entry (r, c): the entry, times the variable's granularity on
+    // a mesh (without a mesh the entry itself, not a product by 1.0). kM selects the mesh at compile
+    // time for the launches of the poll chains, whose no-mesh builds are the code they were (kNoMesh;
+    // kOnMesh: the host selects it when mesh() is set), or tests the pointer (kAnyMesh: the mask, the
+    // identity index and the streaming scan's records).
+    static constexpr int kNoMesh = 0, kOnMesh = 1, kAnyMesh = 2;
+    template <int kM> __device__ __forceinline__ double step_m(int n, int v, int r, int c) const
+    {
+        const double d = entry(n, r, c);
+        if constexpr (kM == kNoMesh) return d;
+        else if constexpr (kM == kOnMesh) return mesh_ptr()[v] * d;
+        else {
+            const double* g = mesh();
+            return g ? g[v] * d : d;
+        }
+    }
+    // variable v's diagonal step at mesh step b = 2^ell (the whole-poll rejection, diag_rejects)
+    template <bool kMesh> __device__ __forceinline__ double diag_step(int v, double b) const
+    {
+        if constexpr (kMesh) return mesh_ptr()[v] * b;
+        else return b;
+    }
     // a full poll's value (np == 0), for the launches that select the poll kind at compile time
     // (the disk index: its full-poll instantiation is the code it was)
-    __device__ __forceinline__ double get_full(int kl, int v, int N) const
+    template <int kM> __device__ __forceinline__ double get_full_m(int kl, int v, int N) const
     {
         if (cands) return cands[(int64_t)kl * ldc + v];
         const int n = 3 * N;
         const int k = kl + k0;
         const int kk = k < n ? k : k - n;
-        const double d = entry(n, rp[v], cp[kk]);
+        const double d = step_m<kM>(n, v, rp[v], cp[kk]);
         return k < n ? xinc[v] + d : xinc[v] - d;
     }
-    __device__ __forceinline__ double get(int kl, int v, int N) const
+    __device__ __forceinline__ double get(int kl, int v, int N) const { return get_m<kAnyMesh>(kl, v, N); }
+    template <int kM> __device__ __forceinline__ double get_m(int kl, int v, int N) const
     {
         if (cands) return cands[(int64_t)kl * ldc + v];
         const int n = polled(N);
@@ -194,17 +233,17 @@ struct CandSrc {
         // variable, v >= n under an xy-only poll, reads row 0 and keeps x's double as it is, no + 0.0)
         const bool held = v >= n;
         const double xv = xinc[v];
-        const double d = entry(n, rp[held ? 0 : v], cp[kk]);
+        const double d = step_m<kM>(n, held ? 0 : v, rp[held ? 0 : v], cp[kk]);
         const double moved = k < n ? xv + d : xv - d;
         return held ? xv : moved;
     }
     // The source selected at compile time (the fused chain's second and third launches, k_fiw.h):
     // kMat is a matrix source, read from cands alone — no generator code in that instantiation and
     // none of its operands held in registers — and never paused by a device state (no mst).
-    template <bool kMat> __device__ __forceinline__ double val(int kl, int v, int N) const
+    template <bool kMat, bool kMesh = false> __device__ __forceinline__ double val(int kl, int v, int N) const
     {
         if constexpr (kMat) return cands[(int64_t)kl * ldc + v];
-        else return cands ? cands[(int64_t)kl * ldc + v] : get(kl, v, N);
+        else return cands ? cands[(int64_t)kl * ldc + v] : get_m<kMesh ? kOnMesh : kNoMesh>(kl, v, N);
     }
     template <bool kMat> __device__ __forceinline__ bool resolve_as()
     {
@@ -398,9 +437,10 @@ struct PrepLds {
     double dred[kPrepU / kWave][4];   // per wave: its share of the displacement bound
 };
 
-template <bool kMat, int PC>
+template <bool kMat, int PC, bool kMesh = false>   // (kMesh: a generated poll on a mesh, CandSrc.step_m)
 __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned char* lds)
 {
+    constexpr int kM = kMesh ? CandSrc::kOnMesh : CandSrc::kNoMesh;
     constexpr int NC = PC;   // candidate slots
     PrepLds<NC>& L = *reinterpret_cast<PrepLds<NC>*>(lds);
     auto& term = L.term;
@@ -451,7 +491,7 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
                         v[c][q] = v[c + 4][q] = a.src.xinc[vv];
                         continue;
                     }
-                    const double d = a.src.entry(np, a.src.rp[vv], a.src.cp[col]);
+                    const double d = a.src.step_m<kM>(np, vv, a.src.rp[vv], a.src.cp[col]);
                     v[c][q] = a.src.xinc[vv] + d;
                     v[c + 4][q] = a.src.xinc[vv] - d;
                 }
@@ -463,7 +503,7 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     if constexpr (kMat) v[c][q] = a.src.cands[(int64_t)k * a.src.ldc + q * N + ii];
-                    else v[c][q] = a.src.get(k, q * N + ii, N);
+                    else v[c][q] = a.src.get_m<kM>(k, q * N + ii, N);
                 }
             }
         }
@@ -472,7 +512,7 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 if constexpr (kMat) base[q] = a.src.cands[q * N + ii];
-                else base[q] = a.src.get(0, q * N + ii, N);
+                else base[q] = a.src.get_m<kM>(0, q * N + ii, N);
             }
         }
         if (obj) {
@@ -501,11 +541,13 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
             if (a.mst_w) {   // (excl, one block of UAVs: uniform) the whole-poll rejection
                 bool rej = true;
                 if (iv) {
-                    const double bb = (double)a.src.b;
-                    rej = diag_rejects(a.src.xinc[ii], bb, x1, 0, pa.tan_half_fov, T3) &&
-                          diag_rejects(a.src.xinc[N + ii], bb, y1, 1, pa.tan_half_fov, T3) &&
+                    const double bb = (double)a.src.b;   // (on a mesh: variable v's step g[v] * 2^ell)
+                    auto ds = [&](int v) { return a.src.diag_step<kMesh>(v, bb); };
+                    rej = diag_rejects(a.src.xinc[ii], ds(ii), x1, 0, pa.tan_half_fov, T3) &&
+                          diag_rejects(a.src.xinc[N + ii], ds(N + ii), y1, 1, pa.tan_half_fov, T3) &&
                           (2 * N >= np ||   // (uniform: over the polled variables only)
-                           diag_rejects(a.src.xinc[2 * N + ii], bb, pa.prev[2 * N + ii], 2, pa.tan_half_fov, T3));
+                           diag_rejects(a.src.xinc[2 * N + ii], ds(2 * N + ii), pa.prev[2 * N + ii], 2,
+                                        pa.tan_half_fov, T3));
                 }
                 const uint64_t keep = __ballot(!rej);
                 if (lane == 0) wrej[wid] = keep == 0;
@@ -702,9 +744,10 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 // fold and the keys are exclusive branches, so the candidate values are dead on the folding
 // wave's path (80 VGPRs: two workgroups, 18 waves, fit a CU). Results are prep_block's bit for bit
 // (the same terms in the same order, the same keys and bound).
-template <bool kGen>
+template <bool kGen, bool kMesh = false>   // (kMesh: as prep_block's)
 __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned char* lds)
 {
+    constexpr int kM = kMesh ? CandSrc::kOnMesh : CandSrc::kNoMesh;
     // kGen: a generated complete poll (K = 2n, n = 3N): workgroup cw takes the columns 3cw .. 3cw + 2
     // of B, slots 0-2 their plus candidates (k = col), slots 3-5 their minus candidates (k = n + col),
     // each B entry drawn once for both; N workgroups
@@ -745,11 +788,11 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
                 const double xv = a.src.xinc[vv];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const double d = a.src.entry(n3, rv, a.src.cp[3 * cw + c]);
+                    const double d = a.src.step_m<kM>(n3, vv, rv, a.src.cp[3 * cw + c]);
                     v[c][q] = xv + d;
                     v[c + 3][q] = xv - d;
                 }
-                base[q] = xv + a.src.entry(n3, rv, a.src.cp[0]);
+                base[q] = xv + a.src.step_m<kM>(n3, vv, rv, a.src.cp[0]);
             }
         } else {
 #pragma unroll
@@ -787,10 +830,12 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
             if (a.mst_w) {   // the whole-poll rejection (uniform)
                 bool rej = true;
                 if (iv) {
-                    const double bb = (double)a.src.b;
-                    rej = diag_rejects(a.src.xinc[ii], bb, x1, 0, pa.tan_half_fov, T3) &&
-                          diag_rejects(a.src.xinc[N + ii], bb, y1, 1, pa.tan_half_fov, T3) &&
-                          diag_rejects(a.src.xinc[2 * N + ii], bb, pa.prev[2 * N + ii], 2, pa.tan_half_fov, T3);
+                    const double bb = (double)a.src.b;   // (on a mesh: variable v's step g[v] * 2^ell)
+                    auto ds = [&](int v) { return a.src.diag_step<kMesh>(v, bb); };
+                    rej = diag_rejects(a.src.xinc[ii], ds(ii), x1, 0, pa.tan_half_fov, T3) &&
+                          diag_rejects(a.src.xinc[N + ii], ds(N + ii), y1, 1, pa.tan_half_fov, T3) &&
+                          diag_rejects(a.src.xinc[2 * N + ii], ds(2 * N + ii), pa.prev[2 * N + ii], 2,
+                                       pa.tan_half_fov, T3);
                 }
                 const uint64_t keep = __ballot(!rej);
                 if (lane == 0) wrej[wid] = keep == 0;
@@ -982,7 +1027,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     }
 }
 
-template <int PC, bool kX = false, bool kGen = false>
+template <int PC, bool kX = false, bool kGen = false, bool kMesh = false>
 __device__ __forceinline__ void prep_body(uint64_t* ts, PrepArgs& a)
 {
     ts_begin(ts);   // profiling only (the chain's first launch: k_common.h)
@@ -997,19 +1042,21 @@ __device__ __forceinline__ void prep_body(uint64_t* ts, PrepArgs& a)
     const int cw = (int)(gridDim.x % 8) == 0 ? (b % 8) * per + b / 8 : b;
     __shared__ __attribute__((aligned(16))) unsigned char lds[sizeof(PrepLds<kX ? PC + 1 : PC>)];
     if constexpr (kX) {   // (N <= kPrepU) a matrix, or a generated complete poll in column triples
-        prep_block_x<kGen>(a, cw, lds);
-    } else if (a.src.cands) {
+        prep_block_x<kGen, kMesh>(a, cw, lds);
+    } else if (!kMesh && a.src.cands) {
         prep_block<true, PC>(a, cw, lds);
     } else {
-        prep_block<false, PC>(a, cw, lds);
+        prep_block<false, PC, kMesh>(a, cw, lds);
     }
     ts_end(ts);
 }
 
 // kPrepC candidates per workgroup, two workgroups per CU
+// kMesh: a generated poll on a mesh (mac_mads_mesh), its own build: without a mesh the code it was
+template <bool kMesh = false>
 __global__ __launch_bounds__(kPrepU) __attribute__((amdgpu_waves_per_eu(4))) void prep_kernel(uint64_t* ts, PrepArgs a)
 {
-    prep_body<kPrepC>(ts, a);
+    prep_body<kPrepC, false, false, kMesh>(ts, a);
 }
 
 // the fused chain's prep over a matrix source: kPrepCX (+1) candidates per workgroup (xbase), a
@@ -1018,10 +1065,11 @@ __global__ __launch_bounds__(kPrepU) __attribute__((amdgpu_waves_per_eu(4))) voi
 // matrix path spill-free, where one kernel holding both paths spilled 13 VGPRs: config 4's prep
 // 20.7 -> 26.1 us). 6 waves per EU beat 5 for the generated path too (prep 17.9 vs 23.7 us with
 // 82 VGPRs and no spill: the two it spills here are off the hot path)
-template <bool kGen>
+template <bool kGen, bool kMesh = false>   // (kMesh: as prep_kernel's; generated polls only)
 __global__ __launch_bounds__(kPrepU + kWave) __attribute__((amdgpu_waves_per_eu(6))) void prep_x_kernel(uint64_t* ts, PrepArgs a)
 {
-    prep_body<kPrepCX, true, kGen>(ts, a);
+    static_assert(kGen || !kMesh, "a mesh belongs to a generated poll");
+    prep_body<kPrepCX, true, kGen, kMesh>(ts, a);
 }
 
 // cands: see CandSrc. Writes disks[k*N + i] (the streaming scan's records).

@@ -307,6 +307,10 @@ struct mac_ctx {
     double reg_w_high = NAN;
     double h_boxes[4 * kRegionsMax];
     DevBuf rboxes, rcount, ritems, rpart, rout;
+    // (profiling on) the fused chain's reports as the next enqueue read them (mac_profile_fused):
+    // reports read, and the sum and the largest of hint word 1, the disks that took one position per
+    // candidate (k_fiw.h kFwHints)
+    std::atomic<int64_t> fw_reports{0}, fw_ident_sum{0}, fw_ident_max{0};
 };
 
 static void set_device(mac_ctx* ctx) { HCK(hipSetDevice(ctx->device)); }
@@ -755,6 +759,8 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
     }
 
     CandSrc isrc = src;
+    // a generated poll on a mesh (mac_mads_mesh): the chains' launches are their own builds (kMesh)
+    const bool mesh = !src.cands && src.mesh() != nullptr;
     const int target = 8 * ctx->cus;
     const int G = (int)std::max<int64_t>(
         1, std::min<int64_t>((target + K - 1) / K, std::max(1, N / kWavesPerBlock)));
@@ -790,8 +796,16 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
         ensure_hints(L);
         volatile int* hw = (volatile int*)L->h_dc.p;
         int bad_now = -1;   // the lane's last poll's report (a hint: it may be an older poll's)
-        if (L->last_chain == 2 && hw[8] >= 0)
+        if (L->last_chain == 2 && hw[8] >= 0) {
             bad_now = hw[8] > kFwCrowdWork || hw[9] > 0 || hw[11] > 0 ? 1 : 0;   // (k_fiw.h kFwHints)
+            if (ctx->profile) {
+                const int64_t id = hw[9];
+                ctx->fw_reports.fetch_add(1, std::memory_order_relaxed);
+                ctx->fw_ident_sum.fetch_add(id, std::memory_order_relaxed);
+                if (id > ctx->fw_ident_max.load(std::memory_order_relaxed))
+                    ctx->fw_ident_max.store(id, std::memory_order_relaxed);
+            }
+        }
         else if (L->last_chain == 1 && hw[0] < (1 << 30))
             bad_now = hw[0] > kBitsMinDisks || hw[4] == kModeTiled ? 1 : 0;
         if (bad_now >= 0) {
@@ -845,10 +859,13 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             hclk::time_point h1, h2, h3;
             if (ctx->host_stats) h1 = hclk::now();
             if (xk && gen_x)
-                hipLaunchKernelGGL(prep_x_kernel<true>, dim3((unsigned)nprep), dim3(kPrepU + kWave), 0, s, tsk, pr);
+                hipLaunchKernelGGL((mesh ? prep_x_kernel<true, true> : prep_x_kernel<true>), dim3((unsigned)nprep),
+                                   dim3(kPrepU + kWave), 0, s, tsk, pr);
             else if (xk)
                 hipLaunchKernelGGL(prep_x_kernel<false>, dim3((unsigned)nprep), dim3(kPrepU + kWave), 0, s, tsk, pr);
-            else hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nprep), dim3(kPrepU), 0, s, tsk, pr);
+            else
+                hipLaunchKernelGGL((mesh ? prep_kernel<true> : prep_kernel<false>), dim3((unsigned)nprep), dim3(kPrepU),
+                                   0, s, tsk, pr);
             HCK(hipGetLastError());
             if (ctx->host_stats) h2 = hclk::now();
             FwArgs fa{};
@@ -881,8 +898,9 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             // the source selects the instantiation of both launches (k_fiw.h kMat): a matrix poll's
             // has no generator code in it; generated and basis-form polls take the other
             const bool mat = src.cands != nullptr;
-            const auto fiw_kern = counts ? (mat ? fiw_kernel<true, true> : fiw_kernel<true, false>)
-                                         : (mat ? fiw_kernel<false, true> : fiw_kernel<false, false>);
+            const auto fiw_kern =
+                counts ? (mat ? fiw_kernel<true, true> : mesh ? fiw_kernel<true, false, true> : fiw_kernel<true, false>)
+                       : (mat ? fiw_kernel<false, true> : mesh ? fiw_kernel<false, false, true> : fiw_kernel<false, false>);
             hipLaunchKernelGGL(fiw_kern, dim3(nfw), dim3(kFwThreads), 0, s, tsw, fa);
             HCK(hipGetLastError());
             if (ctx->host_stats) h3 = hclk::now();
@@ -907,9 +925,15 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             uint64_t* tsf = take_ts(nfin, ts_f, ts_nf);
             // (fb.np: the pipelined loop's update of an xy-only poll, a generated source)
             const bool xy = fb.np != 0 && !mat;
+            // (... and on a mesh: the builds with the scaled values and update)
+            const bool fm = mesh;
             const auto fin2_kern =
-                counts ? (mat ? fin2_kernel<true, true> : xy ? fin2_kernel<true, false, true> : fin2_kernel<true, false>)
-                       : (mat ? fin2_kernel<false, true> : xy ? fin2_kernel<false, false, true> : fin2_kernel<false, false>);
+                counts ? (mat ? fin2_kernel<true, true>
+                          : fm ? (xy ? fin2_kernel<true, false, true, true> : fin2_kernel<true, false, false, true>)
+                          : xy ? fin2_kernel<true, false, true> : fin2_kernel<true, false>)
+                       : (mat ? fin2_kernel<false, true>
+                          : fm ? (xy ? fin2_kernel<false, false, true, true> : fin2_kernel<false, false, false, true>)
+                          : xy ? fin2_kernel<false, false, true> : fin2_kernel<false, false>);
             hipLaunchKernelGGL(fin2_kern, dim3(nfin), dim3(kF2Threads), 0, s,
                                counts ? L->frows.as<unsigned>() : nullptr, counts ? nullptr : L->frows.as<double>(),
                                ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
@@ -970,8 +994,12 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             isrc.ldk = ldk;
         }
         uint64_t* tsk = poll_possible ? take_ts(nrec, ts_c, ts_nc) : nullptr;
-        if (gx5) hipLaunchKernelGGL(prep_x_kernel<true>, dim3((unsigned)nrec), dim3(kPrepU + kWave), 0, s, tsk, pr);
-        else hipLaunchKernelGGL(prep_kernel, dim3((unsigned)nchain), dim3(kPrepU), 0, s, tsk, pr);
+        if (gx5)
+            hipLaunchKernelGGL((mesh ? prep_x_kernel<true, true> : prep_x_kernel<true>), dim3((unsigned)nrec),
+                               dim3(kPrepU + kWave), 0, s, tsk, pr);
+        else
+            hipLaunchKernelGGL((mesh ? prep_kernel<true> : prep_kernel<false>), dim3((unsigned)nchain), dim3(kPrepU), 0,
+                               s, tsk, pr);
         HCK(hipGetLastError());
     }
 
@@ -1044,7 +1072,16 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             const int dedup = iper ? 1 : 0;
             uint64_t* tsi = ts_c >= 0 ? take_ts(nidx, ts_i, ts_ni) : nullptr;
             // (an xy-only poll's kernels are their own instantiations: the full poll's stay as they were)
-            if (isrc.np && isrc.keysT && iper == kIdxPerWide)
+            if (mesh) {   // (... and a mesh's likewise)
+                using IdxKern = void (*)(uint64_t*, CandSrc, int, int, Grid, int, IndexOut);
+                const bool wide = iper == kIdxPerWide, keys = isrc.keysT != nullptr;
+                const IdxKern kern =
+                    isrc.np ? (keys ? (wide ? disk_index_kernel<true, kIdxPerWide, true, true> : disk_index_kernel<true, kIdxPer, true, true>)
+                                    : (wide ? disk_index_kernel<false, kIdxPerWide, true, true> : disk_index_kernel<false, kIdxPer, true, true>))
+                            : (keys ? (wide ? disk_index_kernel<true, kIdxPerWide, false, true> : disk_index_kernel<true, kIdxPer, false, true>)
+                                    : (wide ? disk_index_kernel<false, kIdxPerWide, false, true> : disk_index_kernel<false, kIdxPer, false, true>));
+                hipLaunchKernelGGL(kern, dim3(nidx), dim3(kIdxThreads), 0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
+            } else if (isrc.np && isrc.keysT && iper == kIdxPerWide)
                 hipLaunchKernelGGL((disk_index_kernel<true, kIdxPerWide, true>), dim3(nidx), dim3(kIdxThreads),
                                    0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
             else if (isrc.np && isrc.keysT)
@@ -1238,7 +1275,10 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
     }
     uint64_t* tsf = ts_c >= 0 ? take_ts(nfin, ts_f, ts_nf) : nullptr;
     // (fb.np: the pipelined loop's update of an xy-only poll)
-    const auto fin_kern = fb.np ? finalize_kernel<true> : finalize_kernel<false>;
+    // (... and on a mesh: the builds with the scaled update; a stepper's finalize applies none)
+    const bool fm = mesh && fb.st != nullptr;
+    const auto fin_kern = fm ? (fb.np ? finalize_kernel<true, true> : finalize_kernel<false, true>)
+                             : fb.np ? finalize_kernel<true> : finalize_kernel<false>;
     hipLaunchKernelGGL(fin_kern, dim3(nfin), dim3(kFinThreads), 0, s,
                        L->partial.as<double>(), d_mode, n_poll, n_other, K, N, d_umap, d_spart, d_ncount,
                        counts, ctx->w0, d_vp, d_area, d_obj, fb, tsf);
@@ -1852,6 +1892,20 @@ int32_t mac_profile_split(mac_ctx* ctx, double* prep_ms, double* walk_ms, double
     if (polls) *polls = n;
     return MAC_OK;
     ABI_END
+}
+
+int32_t mac_profile_fused(mac_ctx* ctx, int64_t* reports, int64_t* ident_sum, int64_t* ident_max, int32_t reset)
+{
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (reports) *reports = ctx->fw_reports.load(std::memory_order_relaxed);
+    if (ident_sum) *ident_sum = ctx->fw_ident_sum.load(std::memory_order_relaxed);
+    if (ident_max) *ident_max = ctx->fw_ident_max.load(std::memory_order_relaxed);
+    if (reset) {
+        ctx->fw_reports.store(0, std::memory_order_relaxed);
+        ctx->fw_ident_sum.store(0, std::memory_order_relaxed);
+        ctx->fw_ident_max.store(0, std::memory_order_relaxed);
+    }
+    return MAC_OK;
 }
 
 int32_t mac_profile_kernels(mac_ctx* ctx, double* ms_out, int64_t* launches_out, int32_t n_roles)
@@ -2575,6 +2629,11 @@ struct mac_mads {
     int64_t slot_fallbacks = 0;   // slot waits that timed out (copy + sync instead)
     int route_five = 0;           // the polls are crowded (host_crowded_disks at begin): five-launch chain
     double* ext_best = nullptr;   // mac_mads_best_buffer: the polls' best goes here
+    // the mesh (mac_mads_begin_mesh): the granularity of every variable, host copy and device copy
+    // (empty / null: 1.0 everywhere, the calls without a mesh)
+    std::vector<double> g;
+    DevBuf d_gran;
+    const double* d_g = nullptr;
     int64_t polled_b = 0;        // 2^ell of the poll awaiting its update (0: none)
     double h_enq = 0, h_perm = 0, h_wait = 0, h_post = 0;
     std::chrono::steady_clock::time_point t0;
@@ -2585,6 +2644,7 @@ struct mac_mads {
     ~mac_mads()
     {
         d_x.release();
+        d_gran.release();
         d_feas.release();
         d_st.release();
         d_ring.release();
@@ -2645,9 +2705,10 @@ static bool poll_rejected(const mac_mads* m, int64_t b)
     if (!m->d_prev) return false;
     const int N = m->N;
     const std::vector<double>& T3 = m->L->h_dlim;
-    for (int v = 0; v < m->np; ++v) {   // (the polled variables)
+    for (int v = 0; v < m->np; ++v) {   // (the polled variables; on a mesh v's step is g[v] * b)
         const int q = v / N, i = v % N;
-        if (!diag_rejects(m->x[v], (double)b, m->h_prev[v], q, m->tan_half_fov, T3[i])) return false;
+        const double bv = m->g.empty() ? (double)b : m->g[v] * (double)b;
+        if (!diag_rejects(m->x[v], bv, m->h_prev[v], q, m->tan_half_fov, T3[i])) return false;
     }
     return true;
 }
@@ -2740,7 +2801,7 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
                                double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                                const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
                                mac_mads** out, const mac_cons* cons, bool xy,
-                               const mac_motion* motion = nullptr);
+                               const mac_motion* motion = nullptr, const double* gran = nullptr);
 
 int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
@@ -2775,7 +2836,8 @@ int32_t mac_mads_begin_opts(mac_ctx* ctx, const double* x0, int64_t three_n, con
 static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                                double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                                const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                               mac_mads** out, const mac_cons* cons, bool xy, const mac_motion* motion)
+                               mac_mads** out, const mac_cons* cons, bool xy, const mac_motion* motion,
+                               const double* gran)
 {
     ABI_BEGIN
     if (!out) return fail(MAC_E_INVAL, "null out");
@@ -2850,6 +2912,13 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
             m->d_dlimT = L->dlim.as<double>();
         }
         m->x.assign(x0, x0 + three_n);
+        if (gran) {   // the mesh: validated by the caller (mads_mesh_check), copied here
+            m->g.assign(gran, gran + three_n);
+            m->d_gran.reserve(sizeof(double) * three_n);
+            // (pageable memory: the copy has left m->g when the call returns)
+            HCK(hipMemcpyAsync(m->d_gran.p, m->g.data(), sizeof(double) * three_n, hipMemcpyHostToDevice, s));
+            m->d_g = m->d_gran.as<double>();
+        }
         // pinned staging: [best 16 B][incumbent 8*3N][permutations 4*2n]
         L->h_stage.reserve(16 + sizeof(double) * three_n + sizeof(int) * 2 * n);
         m->hb = (double*)L->h_stage.p;
@@ -2875,7 +2944,17 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
         m->ell = prm->ell0;
         // the run's chain, from its first poll: x0 at mesh step 2^ell0 (the incumbent moves by a few
         // steps over a run; crowding is a property of the UAVs' layout)
-        m->route_five = host_crowded_disks(x0, N, std::ldexp(1.0, prm->ell0), ctx->grid.S) > kBitsMinDisks ? 1 : 0;
+        // (on a mesh the largest step, max_v g[v] 2^ell0; a routing estimate only)
+        const double gmax = m->g.empty() ? 1.0 : *std::max_element(m->g.begin(), m->g.begin() + np);
+        m->route_five = host_crowded_disks(x0, N, gmax * std::ldexp(1.0, prm->ell0), ctx->grid.S) > kBitsMinDisks ? 1 : 0;
+        // A granularity with a non-integer entry: the keys escape to fp32 words or to the identity map
+        // (k_prep.h "Packed keys"), which the fused chain walks one position per candidate; the
+        // five-launch chain's hash still deduplicates them. Measured at config 5 with g_r = 0.125
+        // (tools/mads_granularity_time.py, profiles/mads_granularity.json): 14.6 ms per MPC step
+        // through the five-launch chain against 73.9 ms through the fused one. (The polled variables'
+        // entries: an xy-only poll never steps by g_r.)
+        for (int v = 0; v < np && !m->g.empty(); ++v)
+            if (m->g[v] != std::floor(m->g[v])) m->route_five = 1;
         m->state = prm->seed;
         m->T = (uint64_t)np * (uint64_t)(np - 1) / 2;
         m->per_iter = (uint64_t)np + m->T + 2 * (uint64_t)np;   // ltmads_basis(n_p)'s draws
@@ -2941,6 +3020,7 @@ int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* bes
         src.b = b;
         src.k0 = (int)m->lo;
         src.route_five = m->route_five;
+        src.set_mesh(m->d_g);
         mads_best_of(m, src, Kc, m->lo, true);
     }
     const auto tb = clk::now();
@@ -2979,7 +3059,8 @@ int32_t mac_mads_update(mac_mads* m, double best_obj, int64_t best_idx)
     if (best_idx >= 0 && best_obj < m->f) {
         const int kk = best_idx < n ? (int)best_idx : (int)best_idx - n;
         for (int v = 0; v < n; ++v) {
-            const double d = ltmads_entry(m->state, n, b, m->rp[v], m->cp[kk]);
+            double d = ltmads_entry(m->state, n, b, m->rp[v], m->cp[kk]);
+            if (!m->g.empty()) d = m->g[v] * d;   // the mesh: the device's product (CandSrc.step_m)
             m->x[v] = best_idx < n ? m->x[v] + d : m->x[v] - d;
         }
         m->f = best_obj;
@@ -3046,6 +3127,7 @@ int32_t mac_mads_poll_ahead(mac_mads* m, int32_t ahead, int32_t* done, double* b
     src.b = b;
     src.k0 = (int)m->lo;
     src.route_five = m->route_five;
+    src.set_mesh(m->d_g);
     mads_best_of(m, src, Kc, m->lo, true);
     uint64_t fe = 0;
     mads_wait_best(m, best_obj, best_idx, &fe);
@@ -3073,7 +3155,8 @@ int32_t mac_mads_advance(mac_mads* m, double best_obj, int64_t best_idx, int32_t
     if (better) {   // the current iteration's permutations (rp_next / cp_next)
         const int kk = best_idx < n ? (int)best_idx : (int)best_idx - n;
         for (int v = 0; v < n; ++v) {
-            const double d = ltmads_entry(m->state, n, b, m->rp_next[v], m->cp_next[kk]);
+            double d = ltmads_entry(m->state, n, b, m->rp_next[v], m->cp_next[kk]);
+            if (!m->g.empty()) d = m->g[v] * d;   // the mesh: the device's product (CandSrc.step_m)
             m->x[v] = best_idx < n ? m->x[v] + d : m->x[v] - d;
         }
         m->f = best_obj;
@@ -3203,7 +3286,7 @@ static void mads_run_pipelined(mac_mads* m)
     // the incumbent and the state: x0 (begin's pinned staging holds it), f(x0), ell0
     const auto ta = clk::now();
     HCK(hipMemcpyAsync(dx, m->hx, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    const MadsState st0{m->f, 0, m->ell, 0, 0ull, 0, 0};
+    const MadsState st0{m->f, 0, m->ell, 0, 0ull, 0, 0, m->d_g};
     HCK(hipMemcpy(dst, &st0, sizeof(st0), hipMemcpyHostToDevice));
     int64_t computed = std::min<int64_t>(n_iter, kMadsAhead);
     for (int64_t t = 1; t <= computed; ++t) perms_of(t);
@@ -3239,6 +3322,7 @@ static void mads_run_pipelined(mac_mads* m)
         src.k0 = 0;
         src.mst = dst;
         src.route_five = m->route_five;
+        src.set_mesh(m->d_g);
         FinBest fbm{};
         fbm.st = dst;
         fbm.x = src.xinc;
@@ -3295,7 +3379,7 @@ int32_t mac_mads_run(mac_ctx* ctx, const double* x0, int64_t three_n, const doub
 static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                              const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                             bool xy, const mac_motion* motion = nullptr);
+                             bool xy, const mac_motion* motion = nullptr, const double* gran = nullptr);
 
 int32_t mac_mads_run_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                           double penalty, const double* prev, const double* d_lim, double tan_half_fov,
@@ -3327,14 +3411,14 @@ int32_t mac_mads_run_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const
 static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                              const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                             bool xy, const mac_motion* motion)
+                             bool xy, const mac_motion* motion, const double* gran)
 {
     ABI_BEGIN
     if (!x_out) return fail(MAC_E_INVAL, "null argument");
     mac_mads* m = nullptr;
     // the whole poll: every candidate of the 2 n_p (n_p = 3N, or 2N for the xy-only poll)
     int32_t rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
-                                 xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy, motion);
+                                 xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy, motion, gran);
     if (rc) return rc;
     if (mads_pipelinable(m)) {
         try {
@@ -4478,6 +4562,70 @@ int32_t mac_mads_begin_motion(mac_ctx* ctx, const double* x0, int64_t three_n, c
     if (rc) return rc;
     return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
                            out, cons, xy, motion);
+    ABI_END
+}
+
+// The mesh of mac_mads_run_mesh / mac_mads_begin_mesh: MAC_E_INVAL on a non-zero reserved word or an
+// entry that is not finite and > 0, before the context is touched; *gran = the 3N host doubles, or
+// null when the mesh is the unit one (no mesh, no vector, or every entry exactly 1.0: the _motion call).
+static int32_t mads_mesh_check(const mac_mads_mesh* mesh, int64_t three_n, const double** gran)
+{
+    *gran = nullptr;
+    if (!mesh) return MAC_OK;
+    if (mesh->reserved != 0) return fail(MAC_E_INVAL, "mac_mads_mesh: reserved must be 0");
+    if (!mesh->granularity) return MAC_OK;
+    bool unit = true;
+    for (int64_t v = 0; v < three_n; ++v) {
+        const double g = mesh->granularity[v];
+        if (!(g > 0.0) || !std::isfinite(g))
+            return fail(MAC_E_INVAL, "mac_mads_mesh: granularity[" + std::to_string(v) +
+                                         "] is not finite and > 0");
+        unit = unit && g == 1.0;
+    }
+    if (!unit) *gran = mesh->granularity;
+    return MAC_OK;
+}
+
+int32_t mac_mads_run_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
+                          const mac_mads_opts* opts, const mac_motion* motion, const mac_mads_mesh* mesh)
+{
+    ABI_BEGIN
+    const double* gran = nullptr;
+    int32_t rc = mads_mesh_check(mesh, three_n, &gran);
+    if (rc) return rc;
+    if (!gran)   // the unit mesh: the _motion call, untouched
+        return mac_mads_run_motion(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
+                                   cons, opts, motion);
+    bool xy = false;
+    rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons, xy,
+                         motion, gran);
+    ABI_END
+}
+
+int32_t mac_mads_begin_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi, mac_mads** out,
+                            const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
+                            const mac_mads_mesh* mesh)
+{
+    ABI_BEGIN
+    if (!out) return fail(MAC_E_INVAL, "null out");
+    *out = nullptr;
+    const double* gran = nullptr;
+    int32_t rc = mads_mesh_check(mesh, three_n, &gran);
+    if (rc) return rc;
+    if (!gran)   // the unit mesh: the _motion call, untouched
+        return mac_mads_begin_motion(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
+                                     shard_hi, out, cons, opts, motion);
+    bool xy = false;
+    rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
+                           out, cons, xy, motion, gran);
     ABI_END
 }
 
