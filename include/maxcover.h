@@ -516,6 +516,56 @@ int32_t mac_mads_begin_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, con
                             mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts,
                             const mac_motion* motion, const mac_mads_mesh* mesh);
 
+/* Progressive constraints (src/TDM_Constraints.jl:182-220: cons1_progressive, cons2_progressive,
+ * cons3_progressive; handed to DirectSearch's progressive barrier at src/TDM_STATIC_opt.jl:142-159).
+ * J = n_cons constraints, 1 <= J <= 32; bit j of member[i] says UAV i belongs to constraint j;
+ *   t_i = max(R_i - limit[i], 0.0)   (Julia's max: a NaN difference stays NaN)
+ *   c_j = sum of t_i over constraint j's UAVs, folded from 0.0 in the order i = 0 .. N-1
+ *   h   = sum_j c_j * c_j, folded from 0.0 in the order j = 0 .. J-1 (each product rounded, no FMA)
+ * A point is feasible when h == 0.0 as computed. The arrays are host memory, copied at the call.
+ * MAC_E_INVAL (the message names mac_prog, nothing written, checked before the context is touched):
+ * n_cons outside [0, 32], n_cons > 0 with a null array, a bit at or above n_cons, a non-zero
+ * reserved word, a NaN limit, N > 2048. */
+typedef struct mac_prog {
+    const uint32_t* member;   /* N host words */
+    const double*   limit;    /* N host doubles */
+    int32_t         n_cons;   /* 0: no progressive constraint */
+    int32_t         reserved; /* = 0 */
+    double          h_max0;   /* mac_mads_run_prog: the barrier's first threshold (> 0, +inf allowed);
+                                 negative or NaN: h(x0) when that is > 0, else +inf */
+} mac_prog;                   /* 32 B */
+/* h of the K candidates of a host matrix (3N x K, a candidate per column) into h_out[K], by
+ * prog_h_kernel (k_prog.h). Needs no point list. prog = NULL or n_cons = 0: every h is 0.0. */
+int32_t mac_prog_h_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K, const mac_prog* prog,
+                       double* h_out);
+
+/* mac_mads_run_mesh under progressive constraints: the progressive barrier (Audet & Dennis 2009) as
+ * DESIGN.md section 4 states it. The loop keeps a feasible incumbent F (h == 0) and an infeasible
+ * one I (0 < h <= h_max) and polls both with the iteration's one basis (F first); a candidate that
+ * fails cons3, mac_cons or mac_motion, whose h is NaN or whose h > h_max is not evaluated. The
+ * iteration is dominating (ell + 1), improving (ell stays, h_max drops to the largest candidate h
+ * below I.h) or unsuccessful (ell - 1). x_out is F.x when F exists, else I.x
+ * (src/TDM_STATIC_opt.jl:165-169); x_inf_out (3N, may be NULL) receives I.x when I exists.
+ * stats: f and feasible describe x_out, evaluations = 1 + K per centre polled, successes = the
+ * dominating iterations, feasible_evaluations = the candidates evaluated (= pstats->evaluated).
+ * The loop is stepped by the host: per iteration and centre the mask launch (if any), prog_h_kernel
+ * and the poll chain on one stream, then prog_select_kernel and one read-back of its 64-byte record.
+ * prog = NULL or n_cons = 0: mac_mads_run_mesh itself (pstats untouched). Besides mac_prog's errors:
+ * h(x0) NaN, h(x0) > h_max0 (MAC_E_INVAL, naming mac_prog, before the context is touched). */
+typedef struct mac_mads_prog_stats {
+    int32_t has_feasible, has_infeasible;
+    double  f_feasible, f_infeasible, h_infeasible, h_max;
+    int64_t dominating, improving, unsuccessful;
+    int64_t two_centre_polls;
+    int64_t evaluated;
+} mac_mads_prog_stats;        /* 80 B */
+int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* params, double* x_out, mac_mads_stats* stats,
+                          const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
+                          const mac_mads_mesh* mesh, const mac_prog* prog, double* x_inf_out,
+                          mac_mads_prog_stats* pstats);
+
 /* fp32 candidates (config 3's "fp32" caller path; SURVEY 8(b) "*_f32: coords f32, accum f64"):
  * the candidate matrix (and prev) are uploaded as floats and widened exactly on the device;
  * coverage is then the reference's fp64 predicate on those doubles, areas accumulate in fp64 /
@@ -650,8 +700,10 @@ int32_t mac_profile_split(mac_ctx* ctx, double* prep_ms, double* walk_ms, double
  *   4 coverage_poll_kernel, 5 the crowded-poll shared-entry pass (shared_or_kernel on equal
  *   weights, shared_bits_kernel otherwise), 6 finalize_kernel (five-launch chain), 7 fiw_kernel and
  *   8 fin2_kernel (the fused chain), 9 cons_mask_gen_kernel (the native MADS driver's swarm mask, one
- *   launch per masked poll) (MAC_PROF_ROLES = 10). */
-#define MAC_PROF_ROLES 10
+ *   launch per masked poll), 10 prog_h_kernel and 11 prog_select_kernel (mac_mads_run_prog: one
+ *   prog_h launch per polled centre, none under MAC_POLL_XY, and one select launch per iteration)
+ *   (MAC_PROF_ROLES = 12). */
+#define MAC_PROF_ROLES 12
 int32_t mac_profile_kernels(mac_ctx* ctx, double* ms_out, int64_t* launches_out, int32_t n_roles);
 /* With profiling on, the fused chain's launch-hint reports as the context's later enqueues read them
  * (each poll's finalize writes its report to mapped host words; the lane's next poll reads them, so a

@@ -18,7 +18,7 @@ is what the parity tests exercise. See INTEGRATION.md.
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacCons, MacMotion, cons_mask,
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacProg, MadsProgStats, MacCons, MacMotion, cons_mask,
        set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
@@ -433,6 +433,45 @@ function mesh_granularity(granularity, three_n::Integer)
 end
 
 """
+MacProg — the progressive constraints of src/TDM_Constraints.jl:182-220 (mac_prog, include/maxcover.h):
+bit j of `member[i]` says UAV i belongs to constraint j (1 <= n_cons <= 32), `limit[i]` is its altitude
+limit (r_max), `h_max0` the progressive barrier's first threshold (negative: h(x0), the reference's
+barrier_threshold^2, src/TDM_STATIC_opt.jl:146). `MacProg(r_max)` is cons1_progressive: every UAV in
+one constraint.
+"""
+struct MacProg
+    member::Vector{UInt32}
+    limit::Vector{Float64}
+    n_cons::Int32
+    h_max0::Float64
+end
+MacProg(r_max::Vector{Float64}; h_max0::Float64 = -1.0) =
+    MacProg(fill(UInt32(1), length(r_max)), copy(r_max), Int32(1), h_max0)
+
+struct CProg   # mac_prog's C layout, 32 bytes
+    member::Ptr{UInt32}
+    limit::Ptr{Float64}
+    n_cons::Int32
+    reserved::Int32
+    h_max0::Float64
+end
+
+"mac_mads_prog_stats (include/maxcover.h), 80 bytes."
+struct MadsProgStats
+    has_feasible::Int32
+    has_infeasible::Int32
+    f_feasible::Float64
+    f_infeasible::Float64
+    h_infeasible::Float64
+    h_max::Float64
+    dominating::Int64
+    improving::Int64
+    unsuccessful::Int64
+    two_centre_polls::Int64
+    evaluated::Int64
+end
+
+"""
 mads_run(x0, r_max, ctx; prev, d_lim, tan_half_fov, n_iter, ell0, ell_max, seed, cons, poll_vars) — the whole
 granular-MADS loop inside libmaxcover (complete LTMADS poll generated on the device, cons3 as
 extreme barrier): the batched stand-in for TDM_STATIC_opt.optimize (src/TDM_STATIC_opt.jl:118-169).
@@ -444,8 +483,12 @@ for bit — for the steps where "no height changes need to be explored" (src/TDM
 `:xyr`, the default, is the calls above. `motion::MacMotion` (mac_mads_run_motion) adds cons4 / cons5 /
 cons6 to every poll's mask. `granularity` (mac_mads_run_mesh; `nothing`: the calls above): a number, a pair
 (g_xy, g_r) or 3N numbers laid out as `x0`; variable v then steps by g[v] times the basis's integers, as the
-reference's SetGranularity does (:131-137). Like the rest of this shim, the `poll_vars`, `motion` and
-`granularity` paths have not been executed here. Returns (x, stats::MadsStats).
+reference's SetGranularity does (:131-137). `prog::MacProg` (mac_mads_run_prog): the reference's
+`cons_prog` slot under the progressive barrier; the call then returns
+(x, stats::MadsStats, x_infeasible, pstats::MadsProgStats), x the feasible incumbent when there is one
+(src/TDM_STATIC_opt.jl:165-169) and x_infeasible the infeasible one or `nothing`. Like the rest of this
+shim, the `poll_vars`, `motion`, `granularity` and `prog` paths have not been executed here. Returns
+(x, stats::MadsStats).
 """
 function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                   penalty::Float64 = 1e5, prev::Union{Nothing,Vector{Float64}} = nothing,
@@ -453,7 +496,7 @@ function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
                   n_iter::Integer = 100, ell0::Integer = 2, ell_max::Integer = 6,
                   seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing,
                   poll_vars::Symbol = :xyr, motion::Union{Nothing,MacMotion} = nothing,
-                  granularity = nothing)
+                  granularity = nothing, prog::Union{Nothing,MacProg} = nothing)
     opts = MadsOpts(poll_vars)
     g = granularity === nothing ? nothing : mesh_granularity(granularity, length(x0))
     x = similar(x0)
@@ -461,6 +504,29 @@ function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
     st = Ref{MadsStats}()
     pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
     pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
+    if prog !== nothing
+        length(prog.member) == length(prog.limit) == length(x0) ÷ 3 ||
+            throw(ArgumentError("prog: member and limit hold N values each"))
+        xi = fill(NaN, length(x0))
+        ps = Ref{MadsProgStats}()
+        rcons = cons === nothing ? nothing : Ref(cons)
+        rmot = motion === nothing ? nothing : Ref(CMotion(motion))
+        rmesh = g === nothing ? nothing : Ref(MacMadsMesh(pointer(g), 0))
+        GC.@preserve prev d_lim motion g prog rcons rmot rmesh begin
+            pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)
+            pmot = rmot === nothing ? Ptr{CMotion}(C_NULL) : Base.unsafe_convert(Ptr{CMotion}, rmot)
+            pmesh = rmesh === nothing ? Ptr{MacMadsMesh}(C_NULL) : Base.unsafe_convert(Ptr{MacMadsMesh}, rmesh)
+            cp = Ref(CProg(pointer(prog.member), pointer(prog.limit), prog.n_cons, Int32(0), prog.h_max0))
+            check(ccall((:mac_mads_run_prog, libmaxcover), Int32,
+                        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64},
+                         Ptr{Float64}, Float64, Ref{MadsParams}, Ptr{Float64}, Ref{MadsStats},
+                         Ptr{MacCons}, Ref{MadsOpts}, Ptr{CMotion}, Ptr{MacMadsMesh}, Ref{CProg},
+                         Ptr{Float64}, Ref{MadsProgStats}),
+                        ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, x, st,
+                        pcons, Ref(opts), pmot, pmesh, cp, xi, ps))
+        end
+        return x, st[], (ps[].has_infeasible != 0 ? xi : nothing), ps[]
+    end
     GC.@preserve prev d_lim motion g begin
         if g !== nothing
             rcons = cons === nothing ? nothing : Ref(cons)

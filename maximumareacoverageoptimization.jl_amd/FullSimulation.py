@@ -150,14 +150,26 @@ class Simulation:
     with ``motion=None`` the records and calls are what they were.
     ``granularity``: the MADS mesh of every step (None, a scalar, a pair (g_xy, g_r) or 3N values:
     Context.mads_run, mac_mads_mesh), in all three modes; "auto" then compares with g_r / 2. None:
-    the calls as they were."""
+    the calls as they were.
+    ``cons_prog``: the progressive constraints MADS gets (the reference's cons_prog slot, :23, :86,
+    :97), under the progressive barrier of Context.mads_run(prog=) with the first threshold
+    ``h_max0`` (None: h at each step's MADS input). An entry is a constraint carrying ``mac_prog``
+    data, or a factory called once with the simulation's own ``r_max`` array (the one the r_max rule
+    updates): ``TDM_Constraints.create_cons1_progressive``, or
+    ``functools.partial(create_cons_progressive, i)``. A callable without device data, or a shard of
+    more than one rank, is refused (ValueError): the barrier runs in the single-GPU native loop only.
+    Each record then gains ``h`` (of the step's output), ``has_feasible`` and the counts
+    ``dominating`` / ``improving`` / ``unsuccessful``. ``penalty``: the objective's weight on
+    sum |R_i - r_max_i| (src/TDM_STATIC_opt.jl:97), 1e5 as in the reference; 0 leaves the altitude to
+    the progressive constraint alone."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
                  r_max=None, seed: int = 20250216, ell0: int = 2, ell_max: int = 6,
                  shard=None, gather=None, speculate: bool | None = None, device=None,
                  attribution: bool = False, cons_ext=(), high_interest=None, w_high=None,
-                 poll_vars: str = "xyr", motion=None, velocities=None, granularity=None):
+                 poll_vars: str = "xyr", motion=None, velocities=None, granularity=None,
+                 cons_prog=(), h_max0=None, penalty: float = 1e5):
         if poll_vars not in ("xyr", "xy", "auto"):
             raise ValueError(f"poll_vars must be 'xyr', 'xy' or 'auto', not {poll_vars!r}")
         self.poll_vars = poll_vars
@@ -184,6 +196,9 @@ class Simulation:
         self.d_lim = np.full(N, 10.0) if d_lim is None else np.asarray(d_lim, dtype=np.float64)
         self.r_max = (np.full(N, h_max * self.tan) if r_max is None
                       else np.asarray(r_max, dtype=np.float64).copy())
+        self.penalty = float(penalty)
+        self.h_max0 = h_max0
+        self.cons_prog = self._cons_prog(cons_prog, shard)
         self.fire, self.firepoints = fire, firepoints
         self.N_iter, self.seed, self.ell0, self.ell_max = N_iter, seed, ell0, ell_max
         self.shard = shard          # (rank, world) or None: the whole poll on this GPU
@@ -218,6 +233,30 @@ class Simulation:
         self.t = 0
         self.outputs = []
         self.records = []
+
+    def _cons_prog(self, cons_prog, shard):
+        """The progressive constraints bound to the simulation's r_max (an empty list: none)."""
+        from .TDM_Constraints import merge_mac_prog
+        if callable(cons_prog):
+            cons_prog = [cons_prog]
+        out = []
+        for c in (cons_prog or ()):
+            if not hasattr(c, "mac_prog"):
+                try:
+                    c = c(self.r_max)   # a factory: create_cons1_progressive, partial(create_cons_progressive, i)
+                except Exception:
+                    c = None
+            if not hasattr(c, "mac_prog"):
+                raise ValueError("cons_prog: a progressive constraint without device data (mac_prog) cannot "
+                                 "run in the native MADS driver")
+            out.append(c)
+        if out and shard is not None and shard[1] > 1:
+            raise ValueError("cons_prog: the progressive barrier runs on one GPU only (shard of "
+                             f"{shard[1]} ranks given)")
+        if out and merge_mac_prog(out, self.N)[1]:
+            raise ValueError("cons_prog: the constraints do not fit one mac_prog (different limits, or "
+                             "more than 32)")
+        return out
 
     @staticmethod
     def _boxes(high_interest):
@@ -285,11 +324,15 @@ class Simulation:
             kw["poll_vars"] = pvars
         if self.granularity is not None:
             kw["granularity"] = self.granularity
+        if self.cons_prog:   # (merged per step: the limits are r_max as the rule above left it)
+            from .TDM_Constraints import merge_mac_prog
+            kw["prog"] = merge_mac_prog(self.cons_prog, N)[0]
+            kw["h_max0"] = self.h_max0
         if self.shard is None or self.shard[1] == 1:
-            x_out, st = ctx.mads_run(single_input, self.r_max, 1e5, **kw)
+            x_out, st = ctx.mads_run(single_input, self.r_max, self.penalty, **kw)
         elif self.speculate:
             from .dist import mads_loop_speculative
-            stepper = ctx.mads_stepper(single_input, self.r_max, 1e5, **kw)
+            stepper = ctx.mads_stepper(single_input, self.r_max, self.penalty, **kw)
             try:
                 x_out, st = mads_loop_speculative(stepper, self.gather)
             finally:
@@ -298,7 +341,7 @@ class Simulation:
             from .dist import mads_loop, shard_range
             n_polled = single_input.size if pvars == "xyr" else 2 * N
             lo, hi = shard_range(2 * n_polled, *self.shard)
-            stepper = ctx.mads_stepper(single_input, self.r_max, 1e5, shard=(lo, hi), **kw)
+            stepper = ctx.mads_stepper(single_input, self.r_max, self.penalty, shard=(lo, hi), **kw)
             try:
                 x_out, st = mads_loop(stepper, self.gather)
             finally:
@@ -322,6 +365,12 @@ class Simulation:
                    input=single_input)
         if self.poll_vars != "xyr":   # (the default's records are what they were)
             rec["poll_vars"] = pvars
+        if self.cons_prog:
+            from .TDM_Constraints import prog_h
+            rec["h"] = prog_h([c(x_out) for c in self.cons_prog])
+            rec["has_feasible"] = bool(st["has_feasible"])
+            for k in ("dominating", "improving", "unsuccessful"):
+                rec[k] = int(st[k])
         if self.attribution:   # on the step's (post-removal) list
             rec["owned"], rec["exclusive"], _ = ctx.area_by_disk(x_out)
         if self.high_interest is not None:   # :537-557, on the step's (post-removal) list

@@ -10,7 +10,13 @@ swarm constraints written for the reference's ``cons_ext`` slot; they carry ``ma
 
 ``create_cons4`` (:78-103, velocity cone), ``create_cons5`` (:106-119, target speed) and
 ``create_cons6`` (:122-138, target acceleration) limit the move away from the previous target; they
-carry ``mac_motion`` fields, merged the same way (include/maxcover.h mac_motion)."""
+carry ``mac_motion`` fields, merged the same way (include/maxcover.h mac_motion).
+
+``create_cons1_progressive`` (:182-195) and ``create_cons_progressive`` (:197-219) are the
+progressive constraints of the reference's ``cons_prog`` slot: host callables returning the altitude
+excess c(x) >= 0, carrying ``mac_prog`` fields that ``merge_mac_prog`` turns into one descriptor
+(include/maxcover.h mac_prog) for the progressive barrier of ``TDM_STATIC_opt.mads(cons_prog=)`` and
+``Context.mads_run(prog=)``."""
 from __future__ import annotations
 
 import math
@@ -220,3 +226,88 @@ def merge_mac_cons(constraints):
         else:
             plain.append(c)
     return (merged or None), plain
+
+
+# ---- progressive constraints (src/TDM_Constraints.jl:182-220): altitude excess, handed to MADS's
+# progressive barrier (src/TDM_STATIC_opt.jl:142-159) instead of the extreme one
+
+def prog_term(R, limit) -> float:
+    """Julia's ``max(R - limit, 0.0)``: a NaN difference stays NaN (fmax and Python's max drop it)."""
+    d = float(R) - float(limit)
+    return d if (d > 0.0 or d != d) else 0.0
+
+
+def prog_h(c_values) -> float:
+    """h = sum_j c_j * c_j folded from 0.0 in the order j = 0, 1, ...; each product is rounded
+    before its add (Python floats: no FMA)."""
+    h = 0.0
+    for c in c_values:
+        c = float(c)
+        h = h + c * c
+    return h
+
+
+def _progressive(uavs, r_max):
+    def c(x) -> float:
+        xx = np.asarray(x, dtype=np.float64)
+        N = xx.size // 3
+        rm = np.asarray(r_max, dtype=np.float64)   # read at call time, as createObjective does
+        s = 0.0
+        for i in (range(N) if uavs is None else uavs):          # :186-190
+            s = s + prog_term(xx[2 * N + i], rm[i])
+        return s
+
+    c.mac_prog = {"uavs": uavs, "limit": r_max}
+    return c
+
+
+def create_cons1_progressive(r_max):
+    """src/TDM_Constraints.jl:182-195: c(x) = sum_i max(R_i - r_max_i, 0) over every UAV, folded in
+    the order i = 0..N-1. ``r_max`` is read at call time. Carries ``mac_prog`` data (every UAV a
+    member, limit = r_max) for the device (include/maxcover.h mac_prog)."""
+    return _progressive(None, r_max)
+
+
+def create_cons_progressive(i: int, r_max):
+    """src/TDM_Constraints.jl:197-219 (cons2_progressive, cons3_progressive): the altitude excess
+    max(R_i - r_max_i, 0) of the single UAV ``i`` (0-based). Carries ``mac_prog`` data."""
+    i = int(i)
+    if i < 0:
+        raise ValueError("create_cons_progressive: i is a 0-based UAV index")
+    return _progressive((i,), r_max)
+
+
+MAC_PROG_MAX = 32   # constraints one mac_prog holds (a bit per constraint in member[i])
+
+
+def merge_mac_prog(constraints, N: int | None = None):
+    """One mac_prog mapping {member, limit, n_cons} out of the callables that carry ``mac_prog``
+    data (None when there is none), and the list of the callables that do not. Constraint j is the
+    j-th of ``constraints``: bit j of member[i] says UAV i belongs to it. The descriptor has one
+    limit per UAV, read from the constraints' ``r_max`` now; a constraint whose limits differ from
+    the first one's, or the 33rd, stays a host callable. ``N``: the UAV count (default: the limits'
+    length)."""
+    member = limit = None
+    plain, j = [], 0
+    for c in constraints:
+        data = getattr(c, "mac_prog", None)
+        lim = None if data is None else np.asarray(data["limit"], dtype=np.float64).ravel()
+        if lim is not None and N is not None:
+            lim = lim[:N] if lim.size >= N else None
+        if lim is None or j >= MAC_PROG_MAX or \
+                (limit is not None and not np.array_equal(limit, lim, equal_nan=True)) or \
+                (data["uavs"] is not None and any(u >= lim.size for u in data["uavs"])):
+            plain.append(c)
+            continue
+        if limit is None:
+            limit = np.ascontiguousarray(lim.copy())
+            member = np.zeros(limit.size, dtype=np.uint32)
+        if data["uavs"] is None:
+            member |= np.uint32(1 << j)
+        else:
+            for u in data["uavs"]:
+                member[u] |= np.uint32(1 << j)
+        j += 1
+    if limit is None:
+        return None, plain
+    return {"member": member, "limit": limit, "n_cons": j}, plain

@@ -18,7 +18,7 @@ import time
 import numpy as np
 
 from ._lib import Context, InexactError, default_context, mesh_granularity
-from .TDM_Constraints import merge_mac_cons, merge_mac_motion
+from .TDM_Constraints import merge_mac_cons, merge_mac_motion, merge_mac_prog, prog_h
 from .workloads import SplitMix64, ltmads_basis
 
 PENALTY = 1e5  # :97
@@ -84,6 +84,13 @@ class Status:
         self.cons3_passed = 0
         self.cons3_empty_polls = 0
         self.successes = 0   # polls that moved the incumbent (mac_mads_stats.successes)
+        # under progressive constraints (mads cons_prog=): the iterations by outcome, the polls
+        # around both incumbents and the trial points evaluated (mac_mads_prog_stats)
+        self.dominating = 0
+        self.improving = 0
+        self.unsuccessful = 0
+        self.two_centre_polls = 0
+        self.evaluated = 0
         self.optimization_status = "Unoptimized"
 
 
@@ -94,6 +101,12 @@ class MADSResult:
         self.x = None
         self.i = None
         self.x_cost = np.inf
+        # the infeasible incumbent's objective and h, and the barrier threshold (cons_prog= only)
+        self.i_cost = np.inf
+        self.i_h = None
+        self.h_max = None
+        # per iteration (outcome, F.x, F.f, I.x, I.f, I.h, h_max, centres polled) (cons_prog= only)
+        self.history = []
         self.status = Status()
 
 
@@ -127,7 +140,8 @@ def scaled_basis(B: np.ndarray, g) -> np.ndarray:
 
 
 def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int = 6,
-         seed: int = 20250216, poll_vars: str = "xyr", granularity=None) -> MADSResult:
+         seed: int = 20250216, poll_vars: str = "xyr", granularity=None, cons_prog=(),
+         h_max0=None) -> MADSResult:
     """Granular MADS, complete poll over D = [B, -B] (B an LTMADS-style integer basis whose
     entries are bounded by 2^ell), extreme barrier on cons_ext. Success: ell <- min(ell+1,
     ell_max) (larger steps); failure: ell <- ell-1; stop when ell < 0 (below the granularity
@@ -140,7 +154,13 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
     and the radii are held (MAC_POLL_XY, include/maxcover.h).
     ``granularity``: DirectSearch's SetGranularity (src/TDM_STATIC_opt.jl:131-137) per variable: None,
     a scalar, a pair (g_xy, g_r) or 3N values laid out as x; variable v steps by g[v] times the
-    basis's integers (mac_mads_mesh, include/maxcover.h). None is 1.0 everywhere."""
+    basis's integers (mac_mads_mesh, include/maxcover.h). None is 1.0 everywhere.
+    ``cons_prog``: progressive constraints c_j(x) >= 0 (TDM_Constraints.create_cons1_progressive /
+    create_cons_progressive, or plain callables), handled by the progressive barrier with the
+    threshold ``h_max0`` (mads_prog below); empty: this loop as it is."""
+    if len(cons_prog):
+        return mads_prog(input, obj, cons_ext, cons_prog, h_max0, N_iter, ell0, ell_max, seed,
+                         poll_vars, granularity)
     t0 = time.perf_counter()
     res = MADSResult()
     x = np.asarray(input, dtype=np.float64).copy()
@@ -206,6 +226,140 @@ def mads(input, obj, cons_ext=(), N_iter: int = 100, ell0: int = 2, ell_max: int
         res.x, res.x_cost = x, f
     else:
         res.i = x
+    return res
+
+
+def prog_select(F_f, I_f, I_h, h_max, cands):
+    """Steps 3-7 of the progressive-barrier rule over the evaluated trial
+    points ``cands`` = [(f, h, centre, k), ...] in (centre, k) order: F_f the feasible incumbent's
+    objective or None, (I_f, I_h) the infeasible incumbent's or None. Returns (outcome, bestF,
+    newI, h_new): outcome 'dominating' / 'improving' / 'unsuccessful'; bestF = (f, centre, k) when
+    it replaces F, else None; newI = 'old', None or (f, h, centre, k). A trial point whose objective
+    is NaN or +inf selects nothing (prog_select_kernel reads +inf as "not evaluated")."""
+    cands = [t for t in cands if t[0] == t[0] and t[0] != np.inf]
+    bestF = None
+    for f, h, c, k in cands:
+        if h == 0.0 and (bestF is None or f < bestF[0]):
+            bestF = (f, c, k)
+    improves = bestF is not None and (F_f is None or bestF[0] < F_f)
+    inf_c = [t for t in cands if t[1] > 0.0]
+    has_I = I_h is not None
+    dominating = improves or (has_I and any(
+        h <= I_h and f <= I_f and (h < I_h or f < I_f) for f, h, _, _ in inf_c))
+    improving = not dominating and has_I and any(h < I_h for _, h, _, _ in inf_c)
+    if improving:
+        h_new = max(h for _, h, _, _ in inf_c if h < I_h)
+    else:
+        h_new = I_h if has_I else h_max
+    newI = "old" if has_I and I_h <= h_new else None
+    cur = (I_f, I_h) if newI == "old" else None
+    for t in inf_c:
+        f, h = t[0], t[1]
+        if h <= h_new and (cur is None or f < cur[0] or (f == cur[0] and h < cur[1])):
+            newI, cur = t, (f, h)
+    outcome = "dominating" if dominating else "improving" if improving else "unsuccessful"
+    return outcome, (bestF if improves else None), newI, h_new
+
+
+def mads_prog(input, obj, cons_ext, cons_prog, h_max0=None, N_iter: int = 100, ell0: int = 2,
+              ell_max: int = 6, seed: int = 20250216, poll_vars: str = "xyr",
+              granularity=None) -> MADSResult:
+    """``mads`` under progressive constraints: the progressive barrier of Audet & Dennis (2009) as
+    DESIGN.md section 4 states it (the reference's AddProgressiveCollection,
+    src/TDM_STATIC_opt.jl:142-159). h(x) = sum_j c_j(x)^2; a feasible incumbent F (h == 0) and an
+    infeasible one I (0 < h <= h_max) are both polled with the iteration's one basis; trial points
+    failing ``cons_ext``, with a NaN h or with h > h_max are dropped unevaluated. ``h_max0``: the
+    initial threshold (None, negative or NaN: h(x0) when that is > 0, the reference's
+    barrier_threshold^2, else +inf). With ``obj.poll`` and constraints that all carry ``mac_prog``
+    data h comes from the device (Context.prog_h). Result: ``x`` = F.x, ``i`` = I.x (either may be
+    None), ``x_cost`` / ``i_cost`` / ``i_h`` / ``h_max``."""
+    t0 = time.perf_counter()
+    res = MADSResult()
+    st = res.status
+    x0 = np.asarray(input, dtype=np.float64).copy()
+    n = polled_count(x0.size, poll_vars)
+    g = mesh_granularity(granularity, x0.size)
+    rng = SplitMix64(seed)
+    cons = list(cons_ext)
+    progs = list(cons_prog)
+    dev_prog = None
+    if hasattr(obj, "poll"):
+        dev_prog, plain = merge_mac_prog(progs, x0.size // 3)
+        if plain:
+            dev_prog = None
+
+    def h_of(X):
+        if dev_prog is not None:
+            return np.asarray(obj.ctx.prog_h(X, dev_prog), dtype=np.float64)
+        return np.array([prog_h([c(v) for c in progs]) for v in X], dtype=np.float64)
+
+    def evaluate(X):
+        if hasattr(obj, "poll"):
+            return np.asarray(obj.poll(X)[2], dtype=np.float64)
+        return np.array([obj(v) for v in X], dtype=np.float64)
+
+    h0 = float(h_of(x0[None, :])[0])
+    if h0 != h0:
+        raise ValueError("cons_prog: h(x0) is NaN")
+    given = h_max0 is not None and float(h_max0) >= 0.0
+    h_max = float(h_max0) if given else (h0 if h0 > 0.0 else np.inf)
+    if h0 > h_max:
+        raise ValueError(f"cons_prog: h(x0) = {h0} > h_max0 = {h_max}")
+    f0 = float(evaluate(x0[None, :])[0]) if all(bool(c(x0)) for c in cons) else np.inf
+    st.function_evaluations += 1
+    F = (x0, f0) if h0 == 0.0 else None
+    I = None if h0 == 0.0 else (x0, f0, h0)
+    ell = ell0
+    it = 0
+    while it < N_iter and ell >= 0:
+        it += 1
+        B = scaled_basis(ltmads_basis(n, ell, rng).astype(np.float64), g)
+        centres = [p[0] for p in (F, I) if p is not None]
+        st.two_centre_polls += len(centres) == 2
+        cands, points = [], {}
+        for c, xc in enumerate(centres):
+            X = poll_matrix(xc, B)
+            st.function_evaluations += X.shape[0]
+            h = h_of(X)
+            keep = np.array([all(bool(q(v)) for q in cons) for v in X], dtype=bool)
+            keep &= ~(h != h) & ~(h > h_max)
+            idx = np.flatnonzero(keep)
+            if idx.size:
+                fv = evaluate(X[idx])
+                for k, f in zip(idx, fv):
+                    cands.append((float(f), float(h[k]), c, int(k)))
+                    points[(c, int(k))] = X[k]
+        st.evaluated += len(cands)
+        outcome, bestF, newI, h_new = prog_select(
+            None if F is None else F[1], None if I is None else I[1],
+            None if I is None else I[2], h_max, cands)
+        if bestF is not None:
+            F = (points[bestF[1:]].copy(), bestF[0])
+        if newI is None:
+            I = None
+        elif newI != "old":
+            I = (points[newI[2:]].copy(), newI[0], newI[1])
+        h_max = h_new
+        if outcome == "dominating":
+            ell = min(ell + 1, ell_max)
+            st.dominating += 1
+            st.successes += 1
+        elif outcome == "improving":
+            st.improving += 1
+        else:
+            ell -= 1
+            st.unsuccessful += 1
+        res.history.append((outcome, None if F is None else F[0].copy(), None if F is None else F[1],
+                            None if I is None else I[0].copy(), None if I is None else I[1],
+                            None if I is None else I[2], h_max, len(centres)))
+    st.iteration = it
+    st.runtime_total = time.perf_counter() - t0
+    st.optimization_status = "MeshPrecisionLimit" if ell < 0 else "IterationLimit"
+    res.h_max = h_max
+    if F is not None:
+        res.x, res.x_cost = F
+    if I is not None:
+        res.i, res.i_cost, res.i_h = I
     return res
 
 
@@ -295,6 +449,6 @@ class PollStepper:
 
 def optimize(input, obj, cons_ext, cons_prog, N_iter: int):
     """src/TDM_STATIC_opt.jl:118-222: returns (p.x if feasible else p.i, runtime_total)."""
-    p = mads(input, obj, cons_ext, N_iter)
+    p = mads(input, obj, cons_ext, N_iter, cons_prog=tuple(cons_prog or ()))
     result = p.i if p.x is None else p.x                # :165-169
     return result, p.status.runtime_total               # :219-220

@@ -46,7 +46,7 @@ MAC_STORE_F32 = 1
 PROF_ROLES = ("prep_kernel",  # (role 0: the prep launch, prep_kernel or prep_x_kernel)
               "disk_index_kernel", "walk_setup_kernel", "coverage_tiled_poll_kernel",
               "coverage_poll_kernel", "shared_or_kernel", "finalize_kernel", "fiw_kernel",
-              "fin2_kernel", "cons_mask_gen_kernel")
+              "fin2_kernel", "cons_mask_gen_kernel", "prog_h_kernel", "prog_select_kernel")
 
 ALGOS = {"auto": MAC_ALGO_AUTO, "scan": MAC_ALGO_SCAN, "tiled": MAC_ALGO_TILED,
          "poll": MAC_ALGO_POLL}
@@ -79,6 +79,7 @@ EXPORTS = (
     "mac_cons_mask_motion_f64", "mac_poll_best_motion_f64", "mac_motion_thresholds",
     "mac_mads_run_motion", "mac_mads_begin_motion",
     "mac_mads_run_mesh", "mac_mads_begin_mesh", "mac_profile_fused",
+    "mac_prog_h_f64", "mac_mads_run_prog",
 )
 
 MAC_REGIONS_MAX = 64
@@ -244,6 +245,53 @@ def make_motion(motion=None, anchor=None, vel=None, speed_prev=None, cone_cos: f
     return m
 
 
+class Prog(ctypes.Structure):
+    """mac_prog (include/maxcover.h): the progressive constraints (altitude excess). Bit j of
+    member[i]: UAV i belongs to constraint j; limit[i]: its altitude limit; n_cons = J <= 32;
+    h_max0: the barrier's first threshold (negative or NaN: the default). Built by make_prog, which
+    keeps the arrays alive on the object."""
+    _fields_ = [("member", ctypes.POINTER(ctypes.c_uint32)), ("limit", ctypes.POINTER(ctypes.c_double)),
+                ("n_cons", ctypes.c_int32), ("reserved", ctypes.c_int32), ("h_max0", ctypes.c_double)]
+
+
+class MadsProgStats(ctypes.Structure):
+    """mac_mads_prog_stats (include/maxcover.h)."""
+    _fields_ = [("has_feasible", ctypes.c_int32), ("has_infeasible", ctypes.c_int32),
+                ("f_feasible", ctypes.c_double), ("f_infeasible", ctypes.c_double),
+                ("h_infeasible", ctypes.c_double), ("h_max", ctypes.c_double),
+                ("dominating", ctypes.c_int64), ("improving", ctypes.c_int64),
+                ("unsuccessful", ctypes.c_int64), ("two_centre_polls", ctypes.c_int64),
+                ("evaluated", ctypes.c_int64)]
+
+
+def make_prog(prog=None, member=None, limit=None, n_cons: int | None = None,
+              h_max0: float | None = None) -> Prog | None:
+    """A Prog from a Prog, a mapping / object with member, limit, n_cons (and h_max0) fields (e.g.
+    TDM_Constraints.merge_mac_prog's mapping), or the keyword values; None stays None (no
+    progressive constraint). A given ``h_max0`` overrides the mapping's; None: the default (-1)."""
+    if isinstance(prog, Prog):
+        if h_max0 is not None:
+            prog.h_max0 = float(h_max0)
+        return prog
+    if prog is not None:
+        get = prog.get if hasattr(prog, "get") else lambda k, d=None: getattr(prog, k, d)
+        member, limit, n_cons = get("member"), get("limit"), get("n_cons")
+        if h_max0 is None:
+            h_max0 = get("h_max0")
+    elif member is None and limit is None and n_cons is None:
+        return None
+    mem = None if member is None else np.ascontiguousarray(np.asarray(member).ravel(), dtype=np.uint32)
+    lim = None if limit is None else np.ascontiguousarray(np.asarray(limit, dtype=np.float64).ravel())
+    if mem is not None and lim is not None and mem.size != lim.size:
+        raise ValueError("prog: member and limit hold N values each")
+    p = Prog(mem.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if mem is not None else None,
+             lim.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if lim is not None else None,
+             0 if n_cons is None else int(n_cons), 0, -1.0 if h_max0 is None else float(h_max0))
+    p._keep = (mem, lim)   # the arrays the pointers refer to
+    p.n_uav = mem.size if mem is not None else (lim.size if lim is not None else 0)
+    return p
+
+
 def motion_thresholds(speed_prev: float, a_max: float) -> tuple[float, float]:
     """mac_motion_thresholds: cons6 for one UAV as (q_hi, q_lo): infeasible iff q3 > q_hi or
     q3 <= q_lo, with q3 the squared 3-D move."""
@@ -382,6 +430,12 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_fire_set_grid": ([_vp, _u8p], _i32),
         "mac_mads_begin": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                             ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp)], _i32),
+        "mac_prog_h_f64": ([_vp, _dp, _i64, _i64, ctypes.POINTER(Prog), _dp], _i32),
+        "mac_mads_run_prog": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                               ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats),
+                               ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts), ctypes.POINTER(Motion),
+                               ctypes.POINTER(MadsMesh), ctypes.POINTER(Prog), _dp,
+                               ctypes.POINTER(MadsProgStats)], _i32),
         "mac_mads_poll": ([_vp, ctypes.POINTER(_i32), _dp, _i64p], _i32),
         "mac_mads_update": ([_vp, ctypes.c_double, _i64], _i32),
         "mac_mads_poll_ahead": ([_vp, _i32, ctypes.POINTER(_i32), _dp, _i64p, _i64p], _i32),
@@ -825,6 +879,20 @@ class Context:
                                          out.ctypes.data_as(_u8p)))
         return out[:K].astype(bool)
 
+    def prog_h(self, cands, prog) -> np.ndarray:
+        """mac_prog_h_f64: the progressive constraints' violation h of each candidate (K x 3N rows)
+        under ``prog`` (a Prog, or anything make_prog takes; None: all 0.0). No point list needed."""
+        c = _f64(cands)
+        if c.ndim != 2:
+            raise ValueError("cands must be K x 3N")
+        K, three_n = c.shape
+        out = np.zeros(max(K, 1))
+        pg = make_prog(prog)
+        if pg is not None and pg.n_cons > 0 and pg.n_uav != three_n // 3:
+            raise ValueError("prog: member and limit hold N values each")
+        _check(self._L.mac_prog_h_f64(self._h, _ptr(c), three_n, K, _opt(pg), _ptr(out)))
+        return out[:K]
+
     def cons_mask_dev(self, d_cands, three_n: int, K: int, cons, d_feasible, stream=None) -> None:
         """mac_cons_mask_dev_f64: device pointers (d_feasible: K uint8), ordered on ``stream``."""
         cs = make_cons(cons)
@@ -946,7 +1014,7 @@ class Context:
     def mads_run(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
                  tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2, ell_max: int = 6,
                  seed: int = 20250216, cons=None, poll_vars: str = "xyr", motion=None,
-                 granularity=None):
+                 granularity=None, prog=None, h_max0=None):
         """mac_mads_run: the whole MADS loop in libmaxcover (candidates generated on the device).
         ``cons`` (a Cons, or anything make_cons takes, e.g. TDM_Constraints.merge_mac_cons's
         mapping): the swarm constraints every poll applies on the device (mac_mads_run_cons); None
@@ -955,7 +1023,12 @@ class Context:
         anything make_motion takes): the target-motion constraints on every poll
         (mac_mads_run_motion). ``granularity``: None, a scalar, a pair (g_xy, g_r) or 3N values laid
         out as x0 (mesh_granularity): variable v steps by g[v] times the basis's integers
-        (mac_mads_run_mesh); None keeps the calls above. Returns (x, stats dict)."""
+        (mac_mads_run_mesh); None keeps the calls above. ``prog`` (a Prog, or anything make_prog
+        takes, e.g. TDM_Constraints.merge_mac_prog's mapping): progressive constraints under the
+        progressive barrier, first threshold ``h_max0`` (mac_mads_run_prog); the stats then gain
+        mac_mads_prog_stats' fields and ``x_infeasible`` (the infeasible incumbent or None), and
+        x is the feasible incumbent when there is one. None keeps the calls above.
+        Returns (x, stats dict)."""
         pvars = poll_vars_code(poll_vars)
         x = _f64(x0)
         g = mesh_granularity(granularity, x.size)
@@ -969,6 +1042,21 @@ class Context:
                 _ptr(pv) if pv is not None else None, _ptr(dl) if dl is not None else None,
                 float(tan_half_fov), ctypes.byref(prm), _ptr(out), ctypes.byref(st))
         cs = make_cons(cons)
+        pg = make_prog(prog, h_max0=h_max0)
+        if pg is not None:
+            if pg.n_cons > 0 and pg.n_uav != x.size // 3:
+                raise ValueError("prog: member and limit hold N values each")
+            op, mo = MadsOpts(pvars), make_motion(motion) if motion is not None else None
+            mesh = MadsMesh(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 0) if g is not None else None
+            xi = np.full_like(x, np.nan)
+            ps = MadsProgStats()
+            _check(self._L.mac_mads_run_prog(*args, _opt(cs), ctypes.byref(op), _opt(mo), _opt(mesh),
+                                             ctypes.byref(pg), _ptr(xi), ctypes.byref(ps)))
+            stats = {k: getattr(st, k) for k, _ in MadsStats._fields_}
+            if pg.n_cons > 0:
+                stats.update({k: getattr(ps, k) for k, _ in MadsProgStats._fields_})
+                stats["x_infeasible"] = xi if ps.has_infeasible else None
+            return out, stats
         if g is not None:
             op, mo = MadsOpts(pvars), make_motion(motion) if motion is not None else None
             mesh = MadsMesh(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 0)
@@ -991,13 +1079,18 @@ class Context:
                      tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2,
                      ell_max: int = 6, seed: int = 20250216, shard=None,
                      cons=None, poll_vars: str = "xyr", motion=None,
-                     granularity=None) -> "MadsStepper":
+                     granularity=None, prog=None) -> "MadsStepper":
         """mac_mads_begin: the native loop one poll at a time over the candidate shard
         ``shard`` = (lo, hi) of each poll's 2 n_p candidates (None: the whole poll). ``cons``: as
         mads_run's (mac_mads_begin_cons; every rank of a sharded loop passes the same one).
         ``poll_vars``: as mads_run's (n_p = 3N for "xyr", 2N for "xy": mac_mads_begin_opts).
         ``motion``: as mads_run's (mac_mads_begin_motion; the same on every rank).
-        ``granularity``: as mads_run's (mac_mads_begin_mesh; the same on every rank)."""
+        ``granularity``: as mads_run's (mac_mads_begin_mesh; the same on every rank).
+        ``prog``: refused (ValueError): the stepper, and with it the sharded and speculative loops,
+        has no progressive barrier; use mads_run."""
+        if prog is not None:
+            raise ValueError("mads_stepper: prog (progressive constraints) is not supported by the "
+                             "stepper; use mads_run(prog=)")
         st = MadsStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
                          ell_max, seed, shard, cons, poll_vars, motion, granularity)
         self._steppers.add(st)

@@ -31,6 +31,9 @@
 //   cons_mask_kernel      the swarm constraints (minimum spacing cons8, altitude zone cons7), one
 //                         feasibility byte per candidate: UAVs counting-sorted by x into cells in LDS,
 //                         pairs tested up to the spacing apart; cons_argmin_kernel: the masked poll's argmin (k_cons.h)
+//   prog_h_kernel         the progressive constraints' violation h per candidate (altitude excess folded
+//                         per constraint in UAV order); prog_select_kernel: the progressive barrier's
+//                         update over an iteration's polls, one 64-byte record (k_prog.h)
 //   region_ingest_kernel / region_stats_kernel / region_reduce_kernel  the high-interest boxes: the
 //                         weight override and counts of arriving entries, and per-box / union / covered
 //                         counts and weights of the current list through the tile index (k_regions.h)
@@ -53,3 +56,4 @@
 #include "k_fiw.h"
 #include "k_cons.h"
 #include "k_regions.h"
+#include "k_prog.h"

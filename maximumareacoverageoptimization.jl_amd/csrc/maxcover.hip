@@ -174,6 +174,8 @@ struct Lane {
     DevBuf bdpart, bdarrive, bdout;            // by_disk_kernel: owned words, arrivals; host calls' results
     DevBuf cmask, cbest;                       // masked poll (k_cons.h): feasibility bytes; the chain's own best
     DevBuf motion;                             // mac_motion's per-UAV arrays (k_cons.h MotionArgs): 8N doubles
+    DevBuf prog, progh, progobj, progrec;      // mac_prog (k_prog.h): member and limit; h and the first centre's
+                                               // objectives of an iteration; prog_select_kernel's record
     std::vector<double> h_motion;              // ... as built on the host
     DevBuf prec, cost;                         // prep launch: per-disk records; walk costs
     int um_hist[8] = {};                       // most distinct positions of a disk, last 8 polls
@@ -276,7 +278,8 @@ struct mac_ctx {
     struct Prof { int64_t a, na, b, nb; int64_t K; const int* mode; int algo;
                   int64_t c = -1, nc = 0, f = -1, nf = 0;
                   int64_t role[MAC_PROF_ROLES][2] = {{-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0},
-                                                     {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}}; };
+                                                     {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0},
+                                                     {-1, 0}, {-1, 0}}; };
     std::vector<Prof> prof;                          // recorded launches (guarded by mu)
     DevBuf stamps;
     int64_t stamp_cap = 0, stamp_used = 0;           // in workgroup slots (guarded by mu)
@@ -482,6 +485,17 @@ static void upload_widen(const float* h, int64_t n, DevBuf& stage, double* d_out
     widen_async(stage.as<float>(), n, d_out, s);
 }
 
+// mac_profile_kernels roles written outside the chain's own table (include/maxcover.h)
+static constexpr int kRoleMask = 9, kRoleProgH = 10, kRoleProgSel = 11;
+static_assert(MAC_PROF_ROLES == 12, "the role table");
+
+// prog_h_kernel's launch inside a generated poll (k_prog.h; mac_mads_run_prog)
+struct ProgLaunch {
+    ProgArgs a;
+    double h_max;
+    double* d_h;   // K doubles
+};
+
 static inline CandSrc matrix_src(const double* d_cands, int N)
 {
     CandSrc c{};
@@ -667,7 +681,8 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                          double tan_half_fov, double* d_area, double* d_obj, double* d_best,
                          int64_t idx_base, uint64_t* d_mirror = nullptr, uint64_t mirror_seq = 0,
                          const FinBest* fb_mads = nullptr, unsigned long long* d_feas = nullptr,
-                         const ConsArgs* gcons = nullptr, const MotionArgs* gmot = nullptr)
+                         const ConsArgs* gcons = nullptr, const MotionArgs* gmot = nullptr,
+                         const ProgLaunch* gprog = nullptr)
 {
     const int64_t M = ctx->M;
     int n_poll = N, n_other = 1;
@@ -678,6 +693,7 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
     int64_t ts_i = -1, ts_ni = 0, ts_s = -1, ts_ns = 0, ts_g = -1, ts_ng = 0;   // index, set-up, bits
     int64_t ts_w = -1, ts_nw = 0;                                               // the fused kernel
     int64_t ts_m = -1, ts_nm = 0;                                               // the swarm mask
+    int64_t ts_p = -1, ts_np = 0;                                               // prog_h_kernel
     auto take_ts = [&](int64_t nwg, int64_t& base, int64_t& n) -> uint64_t* {
         if (!ctx->profile) return nullptr;
         std::lock_guard<std::mutex> lk(ctx->mu);
@@ -715,19 +731,21 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
                         ts_w >= 0 ? MAC_ALGO_POLL : tiled ? MAC_ALGO_TILED : MAC_ALGO_SCAN, ts_c, ts_nc,
                         ts_f, ts_nf};
         if (ts_c >= 0) {   // a poll chain: every launch's stamps by role (mac_profile_kernels)
-            const int64_t r[MAC_PROF_ROLES - 1][2] = {{ts_c, ts_nc}, {ts_i, ts_ni}, {ts_s, ts_ns},
+            const int64_t r[kRoleMask][2] = {{ts_c, ts_nc}, {ts_i, ts_ni}, {ts_s, ts_ns},
                                                   {ts_w >= 0 ? -1 : ts_a, ts_w >= 0 ? 0 : ts_na},
                                                   {ts_b, ts_nb}, {ts_g, ts_ng},
                                                   {ts_w >= 0 ? -1 : ts_f, ts_w >= 0 ? 0 : ts_nf},
                                                   {ts_w, ts_nw},
                                                   {ts_w >= 0 ? ts_f : -1, ts_w >= 0 ? ts_nf : 0}};
-            for (int q = 0; q < MAC_PROF_ROLES - 1; ++q) {
+            for (int q = 0; q < kRoleMask; ++q) {
                 p.role[q][0] = r[q][0];
                 p.role[q][1] = r[q][1];
             }
         }
-        p.role[MAC_PROF_ROLES - 1][0] = ts_m;   // (with or without a poll chain)
-        p.role[MAC_PROF_ROLES - 1][1] = ts_nm;
+        p.role[kRoleMask][0] = ts_m;   // (with or without a poll chain)
+        p.role[kRoleMask][1] = ts_nm;
+        p.role[kRoleProgH][0] = ts_p;
+        p.role[kRoleProgH][1] = ts_np;
         ctx->prof.push_back(p);
     };
 
@@ -755,6 +773,18 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
             hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock), (uint32_t)(17 * kConsBlock * S), s, tsm,
                                src, N, *gcons, L->cmask.as<uint8_t>());
         }
+        HCK(hipGetLastError());
+    }
+
+    // ... under progressive constraints (mac_mads_run_prog): h of every candidate, and the byte of a
+    // candidate the barrier drops (h NaN or above h_max) cleared beside the mask's
+    if (gprog && !src.cands && d_obj && K > 0) {
+        const int and_mask = d_mask8 ? 1 : 0;
+        L->cmask.reserve((size_t)K);
+        d_mask8 = L->cmask.as<uint8_t>();
+        uint64_t* tsp = take_ts(K, ts_p, ts_np);
+        hipLaunchKernelGGL(prog_h_kernel, dim3((unsigned)K), dim3(kProgBlock), 0, s, tsp, src, N, gprog->a,
+                           gprog->h_max, gprog->d_h, L->cmask.as<uint8_t>(), and_mask);
         HCK(hipGetLastError());
     }
 
@@ -2026,7 +2056,7 @@ void mac_ctx_destroy(mac_ctx* ctx)
                           &l->cpart, &l->carrive, &l->ctot, &l->clv, &l->prec, &l->cost, &l->nboxU,
                           &l->ncountU, &l->orjobs, &l->pd, &l->dead8, &l->frows, &l->fwhint, &l->fwlist, &l->fwcount,
                           &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout, &l->cmask, &l->cbest,
-                          &l->motion})
+                          &l->motion, &l->prog, &l->progh, &l->progobj, &l->progrec})
             b->release();
         if (l->done) (void)hipEventDestroy(l->done);
 
@@ -2700,15 +2730,17 @@ static int host_crowded_disks(const double* x, int N, double b, double S)
     return n;
 }
 
-static bool poll_rejected(const mac_mads* m, int64_t b)
+// (x: the poll's centre; null: the stepper's incumbent)
+static bool poll_rejected(const mac_mads* m, int64_t b, const double* x = nullptr)
 {
     if (!m->d_prev) return false;
+    if (!x) x = m->x.data();
     const int N = m->N;
     const std::vector<double>& T3 = m->L->h_dlim;
     for (int v = 0; v < m->np; ++v) {   // (the polled variables; on a mesh v's step is g[v] * b)
         const int q = v / N, i = v % N;
         const double bv = m->g.empty() ? (double)b : m->g[v] * (double)b;
-        if (!diag_rejects(m->x[v], bv, m->h_prev[v], q, m->tan_half_fov, T3[i])) return false;
+        if (!diag_rejects(x[v], bv, m->h_prev[v], q, m->tan_half_fov, T3[i])) return false;
     }
     return true;
 }
@@ -4626,6 +4658,358 @@ int32_t mac_mads_begin_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, con
     if (rc) return rc;
     return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
                            out, cons, xy, motion, gran);
+    ABI_END
+}
+
+// ---- progressive constraints (k_prog.h; include/maxcover.h mac_prog)
+
+// mac_prog's checks, before the context is touched. *on: a constraint is present.
+static int32_t prog_check(const mac_prog* p, int64_t three_n, bool* on)
+{
+    *on = false;
+    if (!p) return MAC_OK;
+    if (p->reserved != 0) return fail(MAC_E_INVAL, "mac_prog: reserved must be 0");
+    if (p->n_cons < 0 || p->n_cons > kProgMaxJ)
+        return fail(MAC_E_INVAL, "mac_prog: n_cons = " + std::to_string(p->n_cons) + " outside [0, " +
+                                     std::to_string(kProgMaxJ) + "]");
+    if (p->n_cons == 0) return MAC_OK;
+    if (!p->member || !p->limit) return fail(MAC_E_INVAL, "mac_prog: n_cons > 0 with a null member or limit array");
+    if (three_n < 0) return fail(MAC_E_INVAL, "negative size");
+    if (three_n % 3 != 0)
+        return fail(MAC_E_SIZE, "InexactError: Int64(" + std::to_string(three_n) + "/3)");
+    const int64_t N = three_n / 3;
+    if (N > kProgMaxN)
+        return fail(MAC_E_INVAL, "mac_prog: N = " + std::to_string(N) + " > " + std::to_string(kProgMaxN) +
+                                     " UAVs (the constraint kernel's limit)");
+    const uint32_t bad = p->n_cons == 32 ? 0u : ~((1u << p->n_cons) - 1u);
+    for (int64_t i = 0; i < N; ++i) {
+        if (p->member[i] & bad)
+            return fail(MAC_E_INVAL, "mac_prog: member[" + std::to_string(i) + "] has a bit at or above n_cons");
+        if (p->limit[i] != p->limit[i])
+            return fail(MAC_E_INVAL, "mac_prog: limit[" + std::to_string(i) + "] is NaN");
+    }
+    *on = true;
+    return MAC_OK;
+}
+
+// h of one point on the host, the rule's arithmetic (this file is built with contraction off).
+static double prog_h_host(const double* x, int N, const mac_prog* p)
+{
+    double h = 0.0;
+    for (int j = 0; j < p->n_cons; ++j) {
+        double c = 0.0;
+        for (int i = 0; i < N; ++i) {
+            if (!((p->member[i] >> j) & 1u)) continue;
+            const double d = x[2 * N + i] - p->limit[i];
+            c = c + ((d > 0.0 || d != d) ? d : 0.0);
+        }
+        const double q = c * c;
+        h = h + q;
+    }
+    return h;
+}
+
+// member and limit into the lane's buffer: [limit: N doubles][member: N words]
+static ProgArgs prog_upload(Lane* L, hipStream_t s, int N, const mac_prog* p)
+{
+    L->prog.reserve(sizeof(double) * (size_t)N + sizeof(uint32_t) * (size_t)N);
+    double* d_limit = L->prog.as<double>();
+    uint32_t* d_member = reinterpret_cast<uint32_t*>(d_limit + N);
+    // (pageable sources: the copies have left the caller's arrays when they return)
+    HCK(hipMemcpyAsync(d_limit, p->limit, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, s));
+    HCK(hipMemcpyAsync(d_member, p->member, sizeof(uint32_t) * (size_t)N, hipMemcpyHostToDevice, s));
+    return ProgArgs{d_member, d_limit, (int)p->n_cons};
+}
+
+int32_t mac_prog_h_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K, const mac_prog* prog,
+                       double* h_out)
+{
+    ABI_BEGIN
+    bool on = false;
+    int32_t rc = prog_check(prog, three_n, &on);
+    if (rc) return rc;
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (three_n < 0 || K < 0) return fail(MAC_E_INVAL, "negative size");
+    if (three_n % 3 != 0)
+        return fail(MAC_E_SIZE, "InexactError: Int64(" + std::to_string(three_n) + "/3)");
+    if (K > (int64_t)1 << 30) return fail(MAC_E_INVAL, "K too large");
+    if (K == 0) return MAC_OK;
+    if (!h_out) return fail(MAC_E_INVAL, "null h output");
+    if (!on || three_n == 0) {   // no constraint, or no UAV to exceed anything
+        std::fill(h_out, h_out + K, 0.0);
+        return MAC_OK;
+    }
+    if (!cands) return fail(MAC_E_INVAL, "null candidates");
+    const int N = (int)(three_n / 3);
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t in_bytes = sizeof(double) * (size_t)three_n * (size_t)K;
+    L->cands.reserve(in_bytes);
+    L->progh.reserve(sizeof(double) * (size_t)K);
+    HCK(hipMemcpyAsync(L->cands.p, cands, in_bytes, hipMemcpyHostToDevice, s));
+    const ProgArgs pa = prog_upload(L, s, N, prog);
+    hipLaunchKernelGGL(prog_h_kernel, dim3((unsigned)K), dim3(kProgBlock), 0, s, (uint64_t*)nullptr,
+                       matrix_src(L->cands.as<double>(), N), N, pa, (double)INFINITY, L->progh.as<double>(),
+                       (uint8_t*)nullptr, 0);
+    HCK(hipGetLastError());
+    HCK(hipMemcpyAsync(h_out, L->progh.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, s));
+    HCK(hipStreamSynchronize(s));
+    return MAC_OK;
+    ABI_END
+}
+
+// A launch outside the poll chains into mac_profile_kernels' record (role r, nwg workgroups).
+static uint64_t* prog_take_ts(mac_ctx* ctx, int role, int64_t nwg)
+{
+    if (!ctx->profile) return nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->stamp_used + nwg > ctx->stamp_cap) return nullptr;
+    mac_ctx::Prof p{-1, 0, -1, 0, 0, nullptr, ctx->prof.empty() ? 0 : ctx->prof.back().algo};
+    p.role[role][0] = ctx->stamp_used;
+    p.role[role][1] = nwg;
+    uint64_t* ts = ctx->stamps.as<uint64_t>() + 2 * ctx->stamp_used;
+    ctx->stamp_used += nwg;
+    ctx->prof.push_back(p);
+    return ts;
+}
+
+// The progressive barrier's loop (the rule: DESIGN.md section 4), stepped by the host from the
+// stepper's pieces. Per iteration: one basis; per centre (F, then I) the staging copy, the mask
+// launch (if any), prog_h_kernel and the poll chain on the stepper's stream, the first centre's
+// objectives copied aside (K doubles, device to device) before the second chain overwrites them;
+// then prog_select_kernel and one copy of its record with a stream synchronisation.
+static void mads_run_prog_loop(mac_mads* m, const mac_prog* prog, double h0, double h_max, double* x_out,
+                               double* x_inf_out, mac_mads_prog_stats* ps)
+{
+    mac_ctx* ctx = m->ctx;
+    Lane* L = m->L;
+    hipStream_t s = m->s;
+    const int n = m->n, np = m->np, N = m->N, K = m->K;
+    const ProgArgs pargs = prog_upload(L, s, N, prog);
+    L->progh.reserve(sizeof(double) * 2 * (size_t)K);
+    L->progobj.reserve(sizeof(double) * (size_t)K);
+    L->progrec.reserve(sizeof(ProgRec));
+    double* d_h[2] = {L->progh.as<double>(), L->progh.as<double>() + K};
+    // pinned staging of this loop: per centre [centre 8n][permutations 4*2np][h fill 8K], the record
+    const size_t stage_c = sizeof(double) * (size_t)n + sizeof(int) * 2 * (size_t)np;
+    const size_t stage_sz = ((stage_c + 7) & ~(size_t)7) + sizeof(double) * (size_t)K;
+    PinnedBuf stage;
+    stage.reserve(2 * stage_sz + sizeof(ProgRec));
+    struct Release {
+        PinnedBuf& b;
+        ~Release() { b.release(); }
+    } release{stage};
+    ProgRec* h_rec = reinterpret_cast<ProgRec*>((char*)stage.p + 2 * stage_sz);
+    // a centre's xinc on the device: the lane's buffer holds both
+    L->xinc.reserve(2 * ((stage_c + 255) & ~(size_t)255));
+    char* d_xinc[2] = {(char*)L->xinc.p, (char*)L->xinc.p + ((stage_c + 255) & ~(size_t)255)};
+
+    struct Inc {
+        std::vector<double> x;
+        double f = INFINITY, h = 0.0;
+        bool has = false;
+    } F, I;
+    if (h0 == 0.0) {
+        F.x = m->x;
+        F.f = m->f;
+        F.has = true;
+    } else {
+        I.x = m->x;
+        I.f = m->f;
+        I.h = h0;
+        I.has = true;
+    }
+    int64_t n_dom = 0, n_imp = 0, n_uns = 0, two = 0, evaluated = 0;
+    using clk = std::chrono::steady_clock;
+    while (m->it < m->prm.n_iter && m->ell >= 0) {
+        const auto ta = clk::now();
+        ++m->it;
+        const int64_t b = (int64_t)1 << m->ell;
+        m->rp.swap(m->rp_next);
+        m->cp.swap(m->cp_next);
+        const Inc* cen[2] = {nullptr, nullptr};
+        int nc = 0;
+        if (F.has) cen[nc++] = &F;
+        if (I.has) cen[nc++] = &I;
+        if (nc == 2) ++two;
+        ProgSelArgs sa{};
+        sa.K = K;
+        for (int c = 0; c < nc; ++c) {
+            m->evals += K;
+            if (poll_rejected(m, b, cen[c]->x.data())) {   // cons3 rejects the whole poll: no launch
+                ++m->rejected;
+                continue;
+            }
+            char* hs = (char*)stage.p + (size_t)c * stage_sz;
+            double* hx = reinterpret_cast<double*>(hs);
+            int* hperm = reinterpret_cast<int*>(hx + n);
+            std::copy(cen[c]->x.begin(), cen[c]->x.end(), hx);
+            std::copy(m->rp.begin(), m->rp.end(), hperm);
+            std::copy(m->cp.begin(), m->cp.end(), hperm + np);
+            HCK(hipMemcpyAsync(d_xinc[c], hs, stage_c, hipMemcpyHostToDevice, s));
+            CandSrc src{};
+            src.xinc = reinterpret_cast<const double*>(d_xinc[c]);
+            src.rp = reinterpret_cast<const int*>(src.xinc + n);
+            src.cp = src.rp + np;
+            src.np = m->xy ? np : 0;
+            src.state = m->state;
+            src.b = b;
+            src.k0 = 0;
+            src.route_five = m->route_five;
+            src.set_mesh(m->d_g);
+            ProgLaunch pl{pargs, h_max, d_h[c]};
+            if (m->xy) {   // the radii are held: every candidate's h is the centre's (<= h_max)
+                double* hh = reinterpret_cast<double*>(hs + ((stage_c + 7) & ~(size_t)7));
+                std::fill(hh, hh + K, cen[c]->h);
+                HCK(hipMemcpyAsync(d_h[c], hh, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, s));
+            }
+            enqueue_eval(ctx, L, s, src, N, K, use_tiled(ctx, N, nullptr, n), L->rmax.as<double>(), m->penalty,
+                         m->d_prev, m->d_dlimT, m->d_prev ? L->dlimraw.as<double>() : nullptr, m->tan_half_fov,
+                         nullptr, L->obj.as<double>(), mads_best_ptr(m), 0, nullptr, 0, nullptr,
+                         m->d_feas.as<unsigned long long>(), m->has_cons ? &m->cons : nullptr,
+                         m->has_mot ? &m->mot : nullptr, m->xy ? nullptr : &pl);
+            sa.h[c] = d_h[c];
+            if (c == 0 && nc == 2) {
+                HCK(hipMemcpyAsync(L->progobj.p, L->obj.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, s));
+                sa.obj[c] = L->progobj.as<double>();
+            } else {
+                sa.obj[c] = L->obj.as<double>();
+            }
+        }
+        sa.has_F = F.has ? 1 : 0;
+        sa.has_I = I.has ? 1 : 0;
+        sa.F_f = F.f;
+        sa.I_f = I.f;
+        sa.I_h = I.h;
+        sa.h_max = h_max;
+        hipLaunchKernelGGL(prog_select_kernel, dim3(1), dim3(kProgSelBlock), 0, s,
+                           prog_take_ts(ctx, kRoleProgSel, 1), sa, L->progrec.as<ProgRec>());
+        HCK(hipGetLastError());
+        HCK(hipMemcpyAsync(h_rec, L->progrec.p, sizeof(ProgRec), hipMemcpyDeviceToHost, s));
+        const auto tb = clk::now();
+        if (m->it < m->prm.n_iter) {   // the next iteration's permutations, while the device works
+            const uint64_t ns = m->state + m->per_iter * 0x9E3779B97F4A7C15ull;
+            stream_permutation(ns, (uint64_t)np + m->T + 1, np, m->rp_next);
+            stream_permutation(ns, (uint64_t)np + m->T + np + 1, np, m->cp_next);
+        }
+        const auto tc = clk::now();
+        HCK(hipStreamSynchronize(s));
+        const auto td = clk::now();
+        const ProgRec r = *h_rec;
+        // candidate g = c K + k of this iteration: centre c moved along column k of the basis
+        auto point = [&](int64_t g, std::vector<double>& out) {
+            const Inc* ce = cen[g / K];
+            const int64_t k = g % K;
+            const int kk = k < np ? (int)k : (int)k - np;
+            out = ce->x;
+            for (int v = 0; v < np; ++v) {
+                double d = ltmads_entry(m->state, np, b, m->rp[v], m->cp[kk]);
+                if (!m->g.empty()) d = m->g[v] * d;   // the mesh: the device's product (CandSrc.step_m)
+                out[v] = k < np ? ce->x[v] + d : ce->x[v] - d;
+            }
+        };
+        std::vector<double> xF, xI;
+        const bool improves = (r.outcome & 256) != 0;
+        if (improves) point(r.bestF_g, xF);
+        if (r.newI_g >= 0) point(r.newI_g, xI);
+        if (improves) {
+            F.x.swap(xF);
+            F.f = r.bestF_f;
+            F.has = true;
+        }
+        if (r.newI_g >= 0) {
+            I.x.swap(xI);
+            I.f = r.newI_f;
+            I.h = r.newI_h;
+            I.has = true;
+        } else if (r.newI_g == kProgNone) {
+            I.has = false;
+        }
+        h_max = r.h_new;
+        evaluated += r.evaluated;
+        switch ((int)(r.outcome & 255)) {
+        case 0:
+            m->ell = std::min(m->ell + 1, (int)m->prm.ell_max);
+            ++n_dom;
+            ++m->succ;
+            break;
+        case 1:
+            ++n_imp;
+            break;
+        default:
+            --m->ell;
+            ++n_uns;
+        }
+        m->state += m->per_iter * 0x9E3779B97F4A7C15ull;
+        const auto te = clk::now();
+        m->h_enq += std::chrono::duration<double>(tb - ta).count();
+        m->h_perm += std::chrono::duration<double>(tc - tb).count();
+        m->h_wait += std::chrono::duration<double>(td - tc).count();
+        m->h_post += std::chrono::duration<double>(te - td).count();
+    }
+    const Inc& out = F.has ? F : I;
+    m->x = out.x;
+    m->f = out.f;
+    std::copy(out.x.begin(), out.x.end(), x_out);
+    if (x_inf_out && I.has) std::copy(I.x.begin(), I.x.end(), x_inf_out);
+    if (ps) {
+        ps->has_feasible = F.has ? 1 : 0;
+        ps->has_infeasible = I.has ? 1 : 0;
+        ps->f_feasible = F.has ? F.f : INFINITY;
+        ps->f_infeasible = I.has ? I.f : INFINITY;
+        ps->h_infeasible = I.has ? I.h : 0.0;
+        ps->h_max = h_max;
+        ps->dominating = n_dom;
+        ps->improving = n_imp;
+        ps->unsuccessful = n_uns;
+        ps->two_centre_polls = two;
+        ps->evaluated = evaluated;
+    }
+}
+
+int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
+                          const mac_mads_opts* opts, const mac_motion* motion, const mac_mads_mesh* mesh,
+                          const mac_prog* prog, double* x_inf_out, mac_mads_prog_stats* pstats)
+{
+    ABI_BEGIN
+    bool on = false;
+    int32_t rc = prog_check(prog, three_n, &on);
+    if (rc) return rc;
+    if (!on)   // no progressive constraint: the _mesh call, untouched
+        return mac_mads_run_mesh(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
+                                 cons, opts, motion, mesh);
+    if (!x0 || !x_out) return fail(MAC_E_INVAL, "null argument");
+    const int N = (int)(three_n / 3);
+    const double h0 = prog_h_host(x0, N, prog);
+    if (h0 != h0) return fail(MAC_E_INVAL, "mac_prog: h(x0) is NaN");
+    const bool given = prog->h_max0 >= 0.0;   // (NaN: false)
+    const double h_max = given ? prog->h_max0 : (h0 > 0.0 ? h0 : (double)INFINITY);
+    if (h0 > h_max)
+        return fail(MAC_E_INVAL, "mac_prog: h(x0) = " + std::to_string(h0) + " > h_max0 = " + std::to_string(h_max));
+    const double* gran = nullptr;
+    rc = mads_mesh_check(mesh, three_n, &gran);
+    if (rc) return rc;
+    bool xy = false;
+    rc = mads_opts_check(opts, &xy);
+    if (rc) return rc;
+    mac_mads* m = nullptr;
+    rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
+                         xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy, motion, gran);
+    if (rc) return rc;
+    try {
+        set_device(ctx);
+        mads_run_prog_loop(m, prog, h0, h_max, x_out, x_inf_out, pstats);
+    } catch (...) {
+        mac_mads_destroy(m);
+        throw;
+    }
+    rc = mac_mads_result(m, nullptr, st);
+    mac_mads_destroy(m);
+    return rc;
     ABI_END
 }
 
