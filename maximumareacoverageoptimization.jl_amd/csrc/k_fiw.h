@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "predicate.h"
+#include "fiw_box.h"
 #include "k_common.h"
 #include "k_prep.h"
 #include "k_index.h"
@@ -101,38 +102,13 @@ struct FwArgs {
     FwShared sh;
 };
 
-// Tile range [lo, hi] holding the span (predicate.h tile_span) of every disk (c, r) with
-// a <= c - r, c + r <= b and |c| + r <= m: partial_range's steps (k_prep.h) with a margin 100x
-// wider, which dominates every rounding by which a, b and m — computed from a base disk and the
-// displacement bound — can differ from the values tile_span rounds per disk.
-__device__ __forceinline__ bool sup_range(double a, double b, double m, double g0, double invS, int n,
-                                          int& lo, int& hi)
-{
-    const double ulo = (a - g0) * invS;
-    const double uhi = (b - g0) * invS;
-    const double err = (m + __builtin_fabs(g0)) * invS * 1e-12 + 1e-9;
-    const double flo = __builtin_floor(ulo - err);
-    const double fhi = __builtin_floor(uhi + err);
-    if (!(flo == flo) || !(fhi == fhi)) { lo = 0; hi = n - 1; return true; }
-    if (fhi < 0.0 || flo > (double)(n - 1)) return false;
-    lo = flo < 0.0 ? 0 : (int)flo;
-    hi = fhi > (double)(n - 1) ? n - 1 : (int)fhi;
-    return true;
-}
-
-// The superset box of disk (x0, y0, r0) (candidate 0's) under the displacement bound (dx, dy, dr):
-// it holds the tile span of every live candidate's disk of that UAV. False: empty (no live disk
-// covers anything); NaN anywhere: the whole grid.
+// The superset box of disk (x0, y0, r0) (candidate 0's) under the displacement bound (dx, dy, dr)
+// (fiw_box.h sup_box_tiles: shared with the host). False: empty; NaN anywhere: the whole grid.
 __device__ __forceinline__ bool sup_box(double x0, double y0, double r0, double dx, double dy, double dr,
                                         const Grid& g, int4& B)
 {
-    const double R = r0 + dr;
-    if (!(R > 0.0) && R == R) return false;
     int a0, a1, b0, b1;
-    if (!sup_range(x0 - dx - R, x0 + dx + R, __builtin_fabs(x0) + dx + R, g.gx0, g.invS, g.nTx, a0, a1))
-        return false;
-    if (!sup_range(y0 - dy - R, y0 + dy + R, __builtin_fabs(y0) + dy + R, g.gy0, g.invS, g.nTy, b0, b1))
-        return false;
+    if (!sup_box_tiles(x0, y0, r0, dx, dy, dr, g.gx0, g.gy0, g.invS, g.nTx, g.nTy, a0, a1, b0, b1)) return false;
     B = make_int4(a0, a1, b0, b1);
     return true;
 }
@@ -167,6 +143,34 @@ __device__ __forceinline__ DiskRec key_disk(const CandSrc& s, uint32_t key, int 
     if (key != kKeyEsc) return word_disk(key, bx, by, br);
     return make_disk(src_val<kMat, kMesh>(s, k, jj, N), src_val<kMat, kMesh>(s, k, N + jj, N),
                      src_val<kMat, kMesh>(s, k, 2 * N + jj, N));
+}
+
+// A thread's own per-candidate words (k = kFwPer tid + j, j < kFwPer; thread 0 also k = kFwMaxK) to
+// an LDS array of one word per candidate (buf: 16-B aligned for 32-bit words, 8-B for 16-bit ones):
+// three stores of four words when all kFwPer are candidates (k < K), else word by word (the last
+// thread with candidates).
+template <typename T>
+__device__ __forceinline__ void own_store(T* buf, const T (&v)[kFwPer + 1], int tid, int K)
+{
+    typedef T V4 __attribute__((ext_vector_type(4)));
+    static_assert(kFwPer % 4 == 0 && (kFwPer * sizeof(T)) % sizeof(V4) == 0, "whole, aligned accesses");
+    const int b = tid * kFwPer;
+    if (b + kFwPer <= K) {
+#pragma unroll
+        for (int c = 0; c < kFwPer / 4; ++c) {
+            V4 q;
+            q.x = v[4 * c];
+            q.y = v[4 * c + 1];
+            q.z = v[4 * c + 2];
+            q.w = v[4 * c + 3];
+            reinterpret_cast<V4*>(buf + b)[c] = q;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kFwPer; ++j)
+            if (b + j < K) buf[b + j] = v[j];
+    }
+    if (tid == 0 && K > kFwMaxK) buf[kFwMaxK] = v[kFwPer];
 }
 
 #ifdef MAC_DIAG
@@ -219,15 +223,16 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
     //   wbuf: hash: a candidate of each position (owner_of)
     //   wbuf: -                                | walk: slice lane constants + staging;
     //                                            in-place shared decisions: coverage words
-    __shared__ uint32_t xbuf[kFwMaxK + 1];
-    __shared__ double tabbuf[kFwMaxK + 1];
-    __shared__ uint16_t zbuf[kFwMaxK + 1];
+    __shared__ __attribute__((aligned(16))) uint32_t xbuf[kFwMaxK + 1];   // (own_store)
+    __shared__ __attribute__((aligned(16))) double tabbuf[kFwMaxK + 1];
+    __shared__ __attribute__((aligned(8))) uint16_t zbuf[kFwMaxK + 1];
     constexpr int kSl4 = kFwKPB * 16, kSlx = kFwKPB * 4, kS32 = (kFwCH + 4) * 16, kSix = kFwCH * 4,
                   kSw = kFwCH * 8;
     constexpr int kWB = kSl4 + kSlx + kS32 + kSix + kSw;
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[kWB];
     static_assert(sizeof(uint64_t) * (kFwMaxK + 1) <= kWB, "coverage words fit the walk buffer");
     static_assert(sizeof(int) * (kFwDirect + 1) <= sizeof(double) * (kFwMaxK + 1), "direct table fits");
+    constexpr int kFwClr = 4 * kFwThreads;   // direct-table slots cleared ahead of D
     __shared__ double2 shp[kFwShE];
     __shared__ double shw[kFwShE];
     __shared__ int shidx[kFwCH];
@@ -311,18 +316,27 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
             ncnt = 0;
             ninner = 0u;
         }
+        // the direct table's first kFwClr slots cleared while the round trip above is in flight
+        // (one 16-B store a thread: nothing here waits for a load), the barrier of the escape
+        // vote below between these stores and the first mark. A poll of small steps needs no
+        // more (its table has (2 Dx + 1)(2 Dy + 1)(Dr + Dl + 1) + 1 slots); a larger table clears
+        // its rest once D is known, behind a barrier of its own.
+        reinterpret_cast<int4*>(table)[tid] = make_int4(0, 0, 0, 0);
         // the key words (failed: the dead word) and failure bits into LDS, this thread's own
         // candidates (no barrier needed to read them back): no per-candidate registers stay live
         // through the index (the walk needs every register it can get)
         bool esc = false;
+        {
+            uint32_t kw[P];
+            uint16_t zw[P];
 #pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int k = kof(j);
-            esc |= k < K && !dj[j] && pq[j] == kKeyEsc;
-            if (k < K) {
-                kx[k] = dj[j] ? kDeadWord : pq[j];
-                zbuf[k] = dj[j] ? (uint16_t)0x8000 : (uint16_t)0;
+            for (int j = 0; j < P; ++j) {
+                esc |= kof(j) < K && !dj[j] && pq[j] == kKeyEsc;
+                kw[j] = dj[j] ? kDeadWord : pq[j];
+                zw[j] = dj[j] ? (uint16_t)0x8000 : (uint16_t)0;
             }
+            own_store(kx, kw, tid, K);
+            own_store(zbuf, zw, tid, K);
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {
@@ -367,7 +381,11 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         }
         // ---- lower neighbours: disks j < i whose boxes overlap box i
         if (rany) {
+            // (fiw_box.h: a dozen operations reject a disk whose box cannot reach box i — nearly
+            // every one of a spread-out poll — and only the others pay for their box)
+            const BoxPre bp = box_pre(RG.x, RG.y, RG.z, RG.w, dmx, dmy, g.gx0, g.gy0, g.S, g.invS);
             auto test = [&](int j, double x0, double y0, double r0) {
+                if (box_pre_rejects(bp, x0, y0, r0 + dmr)) return;
                 int4 B;
                 if (sup_box(x0, y0, r0, dmx, dmy, dmr, g, B) && box_overlap(B, RG)) {
                     const int p = atomicAdd(&ncnt, 1);
@@ -403,28 +421,40 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         const int nslot = dfits && nrd >= 1 ? (2 * Dx + 1) * nyd * nrd : 0;
         bool direct = dfits && nrd >= 1 && (double)Dx == dmx && (double)Dy == dmy && (double)Dr == dmr &&
                       (double)Dl == dml && nslot + 1 <= kFwDirect;
-        if (direct) {
-            for (int q = tid; q <= nslot; q += kFwThreads) table[q] = 0;
+        // (the table's first kFwClr slots were cleared during the first round trip, a barrier ago)
+        if (direct && nslot + 1 > kFwClr) {   // (uniform)
+            for (int q = kFwClr + tid; q <= nslot; q += kFwThreads) table[q] = 0;
+            lds_barrier();   // (the row runs' loads stay in flight)
         }
-        lds_barrier();   // (the table is cleared; the row runs' loads stay in flight)
         MAC_FW_STAMP(15);
         bool miss = false;
-        if (direct) {   // per candidate its slot (zbuf, beside the failure bit); branch-free
+        if (direct) {   // per candidate its slot (zbuf, beside the failure bit); branch-free, integers only
+            // A disk with r = br + (double)dr <= 0 covers nothing and goes to the dead slot, as a
+            // failed candidate. dr is an integer in [-512, 511], so the sum's sign is the exact
+            // sum's (an addition never rounds a non-zero sum to zero): br + (double)dr > 0 exactly
+            // when dr >= floor(-br) + 1 =: drlive (512, no dr at all, when br is NaN). The two lines
+            // after the clamp hold drlive to the sum itself: they change nothing.
+            const double tl = __builtin_floor(-br) + 1.0;
+            int drlive = !(br == br) ? 512 : tl <= -512.0 ? -512 : tl >= 512.0 ? 512 : (int)tl;
+            if (drlive < 512 && !(br + (double)drlive > 0.0)) ++drlive;
+            if (drlive > -512 && br + (double)(drlive - 1) > 0.0) --drlive;
+            const int sdx = nyd * nrd, sbase0 = (Dx * nyd + Dy) * nrd + Dl;
+            const unsigned wx = 2u * (unsigned)Dx, wy = 2u * (unsigned)Dy, wr = (unsigned)(Dr + Dl);
+            uint16_t zw[P];
 #pragma unroll
             for (int j = 0; j < P; ++j) {
                 const int k = kof(j);
                 const uint32_t w = pq[j];
                 const int dx = (int)(w << 21) >> 21, dy = (int)(w << 10) >> 21, dr = (int)w >> 22;
-                // (r <= 0 covers nothing: the dead slot, as a failed candidate)
-                const bool live = k < K && !dj[j] && br + (double)dr > 0.0;
-                const bool inr = dx >= -Dx && dx <= Dx && dy >= -Dy && dy <= Dy && dr >= -Dl && dr <= Dr;
+                const bool live = k < K && !dj[j] && dr >= drlive;
+                const bool inr = (unsigned)(dx + Dx) <= wx && (unsigned)(dy + Dy) <= wy &&
+                                 (unsigned)(dr + Dl) <= wr;
                 miss |= live && !inr;
-                const int sl = live && inr ? ((dx + Dx) * nyd + (dy + Dy)) * nrd + (dr + Dl) : nslot;
-                if (k < K) {
-                    table[sl] = 1;
-                    zbuf[k] = (uint16_t)((dj[j] ? 0x8000 : 0) | sl);
-                }
+                const int sl = live && inr ? sbase0 + dx * sdx + dy * nrd + dr : nslot;
+                zw[j] = (uint16_t)((dj[j] ? 0x8000 : 0) | sl);
+                if (k < K) table[sl] = 1;
             }
+            own_store(zbuf, zw, tid, K);
         }
         MAC_FW_STAMP(13);
         {   // any miss: the hash (an LDS word, not __syncthreads_or: that would wait for the row runs)
@@ -540,14 +570,32 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         }
         // per candidate its position (this thread's own zbuf words: slot -> position), read
         // before the barrier: the table's words become the position credits after it
+        // (four candidates at a time where all kFwPer are candidates: one 8-B read of their zbuf
+        // words, the four table reads issued together, one 8-B write; else word by word)
+        {
+            auto pos_of = [&](uint16_t zb, int k) -> uint16_t {
+                const int sl = zb & 0x7FFF;
+                const int u = ident ? k : direct ? table[sl] : table[sl] & ((1 << kFwIdBits) - 1);
+                return (uint16_t)(u | (zb & 0x8000));
+            };
+            typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
+            const int b = tid * kFwPer;
+            if (b + kFwPer <= K) {
 #pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int k = kof(j);
-            if (k >= K) continue;
-            const uint16_t zb = zbuf[k];
-            const int sl = zb & 0x7FFF;
-            const int u = ident ? k : direct ? table[sl] : table[sl] & ((1 << kFwIdBits) - 1);
-            cinfo[k] = (uint16_t)(u | (zb & 0x8000));
+                for (int c = 0; c < kFwPer / 4; ++c) {
+                    u16x4 q = reinterpret_cast<const u16x4*>(zbuf + b)[c];
+                    q.x = pos_of(q.x, b + 4 * c);
+                    q.y = pos_of(q.y, b + 4 * c + 1);
+                    q.z = pos_of(q.z, b + 4 * c + 2);
+                    q.w = pos_of(q.w, b + 4 * c + 3);
+                    reinterpret_cast<u16x4*>(cinfo + b)[c] = q;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kFwPer; ++j)
+                    if (b + j < K) cinfo[b + j] = pos_of(zbuf[b + j], b + j);
+            }
+            if (tid == 0 && K > kFwMaxK) cinfo[kFwMaxK] = pos_of(zbuf[kFwMaxK], kFwMaxK);
         }
         lds_barrier();
         if (hashed) {

@@ -59,9 +59,16 @@ def main():
            "walk_us": verdict([r["split_ms_per_poll"]["walk"] * 1e3 for r in ab["A"]],
                               [r["split_ms_per_poll"]["walk"] * 1e3 for r in ab["B"]]),
            "plain_ms_per_step": verdict([r["ms_per_step"] for r in pl["A"]], [r["ms_per_step"] for r in pl["B"]])}
+    keys = ["chain_us", "walk_us", "plain_ms_per_step"]
+    # per launch role, where both builds stamped it (the fused chain: prep, fiw, fin2)
+    for role in ("prep_kernel", "fiw_kernel", "fin2_kernel"):
+        if all(r["kernels_avg_us"].get(role) is not None for v in "AB" for r in ab[v]) and ab["A"] and ab["B"]:
+            out[role + "_us"] = verdict([r["kernels_avg_us"][role] for r in ab["A"]],
+                                        [r["kernels_avg_us"][role] for r in ab["B"]])
+            keys.append(role + "_us")
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
-    for k in ("chain_us", "walk_us", "plain_ms_per_step"):
+    for k in keys:
         print(k, {q: out[k][q] for q in ("A_median", "B_median", "A_range", "B_range", "median_difference",
                                          "every_B_below_every_A", "difference_over_noise", "faster")})
 
