@@ -41,6 +41,10 @@ static constexpr int kTiledMaxN = 2048;       // the per-candidate walk keeps al
                                               // workgroup per disk: a per-disk walk for K = 1)
 static constexpr double kPollCostRatio = 4.0; // poll walk if its visits <= 4x the other's
 
+// (host only, this file's own: they read the constants above and the kernels' names unqualified)
+#include "eval_plan.h"
+#include "kernel_select.h"
+
 // ------------------------------------------------------------------ errors
 
 static thread_local std::string g_last_error;
@@ -274,7 +278,9 @@ struct mac_ctx {
     // launch when the device picks the walk (mode != null): the launch that ran is read.
     // c / f: the chain's first launch (the prep) and its last (finalize), whose
     // stamps give the whole poll chain's device span (-1: not stamped)
-    // (role stamps, mac_profile_kernels: [r] = {first slot, slots} of launch role r, -1: none)
+    // (role stamps, mac_profile_kernels: [r] = {first slot, slots} of launch role r, -1: none; a poll
+    // chain's launches take their stamps under their roles, and a, b, c, f are read off them when
+    // the call is recorded: EvalRun::prof_end)
     struct Prof { int64_t a, na, b, nb; int64_t K; const int* mode; int algo;
                   int64_t c = -1, nc = 0, f = -1, nf = 0;
                   int64_t role[MAC_PROF_ROLES][2] = {{-1, 0}, {-1, 0}, {-1, 0}, {-1, 0}, {-1, 0},
@@ -485,16 +491,12 @@ static void upload_widen(const float* h, int64_t n, DevBuf& stage, double* d_out
     widen_async(stage.as<float>(), n, d_out, s);
 }
 
-// mac_profile_kernels roles written outside the chain's own table (include/maxcover.h)
+// mac_profile_kernels' launch roles (include/maxcover.h): the poll chains' own, then the launches
+// beside them
+static constexpr int kRolePrep = 0, kRoleIndex = 1, kRoleSetup = 2, kRoleTiledPoll = 3, kRolePoll = 4,
+                     kRoleShared = 5, kRoleFin = 6, kRoleFiw = 7, kRoleFin2 = 8;
 static constexpr int kRoleMask = 9, kRoleProgH = 10, kRoleProgSel = 11;
 static_assert(MAC_PROF_ROLES == 12, "the role table");
-
-// prog_h_kernel's launch inside a generated poll (k_prog.h; mac_mads_run_prog)
-struct ProgLaunch {
-    ProgArgs a;
-    double h_max;
-    double* d_h;   // K doubles
-};
 
 static inline CandSrc matrix_src(const double* d_cands, int N)
 {
@@ -660,41 +662,28 @@ static bool use_tiled(mac_ctx* ctx, int N, const double* h_cands, int64_t three_
     return visits < 0.5 * (double)ctx->M * (double)N;
 }
 
-// The poll walk's chain (prep keys and records, disk index, walk choice, poll kernel) runs for this
-// evaluation: the tiled family, candidates and entries present, and the poll walk allowed.
-static bool poll_walk_possible(const mac_ctx* ctx, int N, int K, bool tiled)
-{
-    return tiled && N > 0 && ctx->M > 0 &&
-           (ctx->algo == MAC_ALGO_POLL || N > kTiledMaxN ||
-            ((ctx->algo == MAC_ALGO_AUTO || ctx->algo == MAC_ALGO_TILED) && K >= kPollMinK));
-}
+// ---- one evaluation
 
-// Enqueue the prep launch + index + walks + finalize (+ argmin) on stream s. All pointers device.
-// area_out/obj_out may be null; best may be null.
-// d_dlimT: cons3 thresholds per UAV (host calls), else d_dlim_raw: the raw d_lim, thresholded
-// where it is read (device calls).
 static thread_local std::chrono::steady_clock::time_point t_poll_entry;   // (MAXCOVER_HOST_STATS)
 
-static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& src, int N,
-                         int K, bool tiled, const double* d_rmax, double penalty,
-                         const double* d_prev, const double* d_dlimT, const double* d_dlim_raw,
-                         double tan_half_fov, double* d_area, double* d_obj, double* d_best,
-                         int64_t idx_base, uint64_t* d_mirror = nullptr, uint64_t mirror_seq = 0,
-                         const FinBest* fb_mads = nullptr, unsigned long long* d_feas = nullptr,
-                         const ConsArgs* gcons = nullptr, const MotionArgs* gmot = nullptr,
-                         const ProgLaunch* gprog = nullptr)
-{
-    const int64_t M = ctx->M;
-    int n_poll = N, n_other = 1;
-    const int* d_mode = nullptr;
-    // Profiling: the measured walk launches stamp their own workgroups' start / end times
-    // (k_common.h), so measuring adds no packet, event or dependency to the stream.
-    int64_t ts_a = -1, ts_na = 0, ts_b = -1, ts_nb = 0, ts_c = -1, ts_nc = 0, ts_f = -1, ts_nf = 0;
-    int64_t ts_i = -1, ts_ni = 0, ts_s = -1, ts_ns = 0, ts_g = -1, ts_ng = 0;   // index, set-up, bits
-    int64_t ts_w = -1, ts_nw = 0;                                               // the fused kernel
-    int64_t ts_m = -1, ts_nm = 0;                                               // the swarm mask
-    int64_t ts_p = -1, ts_np = 0;                                               // prog_h_kernel
-    auto take_ts = [&](int64_t nwg, int64_t& base, int64_t& n) -> uint64_t* {
+// What the pieces of one enqueue_eval call share: the request and its plan, the buffers of the
+// launches ahead of the chains, and the call's profile record.
+// Profiling: the measured launches stamp their own workgroups' start / end times (k_common.h), so
+// measuring adds no packet, event or dependency to the stream. Each launch takes its slots under
+// its role (mac_profile_kernels); the scan and the small-batch walk, outside the chains, under a / na.
+struct EvalRun {
+    mac_ctx* ctx;
+    Lane* L;
+    hipStream_t s;
+    const EvalReq& rq;
+    const EvalPlan& pl;
+    double* d_vp = nullptr;             // per-candidate penalty (or +inf: cons3)
+    const uint8_t* d_mask8 = nullptr;   // a generated poll's feasibility bytes (mask, prog_h)
+    const int* d_mode = nullptr;        // the five-launch chain: the walk the device chose
+    mac_ctx::Prof prof{-1, 0, -1, 0, 0, nullptr, 0};
+
+    uint64_t* take_ts(int64_t nwg, int64_t& base, int64_t& n)
+    {
         if (!ctx->profile) return nullptr;
         std::lock_guard<std::mutex> lk(ctx->mu);
         if (ctx->stamp_used + nwg > ctx->stamp_cap) return nullptr;   // full: not recorded
@@ -702,621 +691,620 @@ static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const CandSrc& sr
         n = nwg;
         ctx->stamp_used += nwg;
         return ctx->stamps.as<uint64_t>() + 2 * base;
-    };
-    // the objective's penalty and cons3 (the prep launch: one sequential chain per candidate)
-    const PenArgs pa{d_rmax, d_prev, d_dlimT, d_dlim_raw, tan_half_fov};
-    double* d_vp = nullptr;            // per-candidate penalty (or +inf: cons3)
-    const double* d_spart = nullptr;   // poll walk: shared-entry rows
-    const int* d_umap = nullptr;       // poll walk: candidate -> distinct-disk position
-    const int* d_ncount = nullptr;
-    int counts = 0;                    // poll walk with equal weights: integer count rows
-    int bits_on = 0;                   // the shared-entry pass's launch hint (walk set-up)
-    if (d_obj) {
-        L->vp.reserve(sizeof(double) * (size_t)std::max(K, 1));
-        d_vp = L->vp.as<double>();
     }
-    const bool big = N > kTiledMaxN;
-    // the poll chain's walk: forced by the algorithm option (or N past the per-candidate walk's
-    // LDS limit), else 0 = the device's choice (k_poll_shared.h walk_choice)
-    const int walk_forced = (ctx->algo == MAC_ALGO_POLL || big) ? kModePoll
-                          : ctx->algo == MAC_ALGO_TILED ? kModeTiled : 0;
-    const bool poll_possible = poll_walk_possible(ctx, N, K, tiled);
-    // candidates per index thread: 3 (K <= 3073), 6 (K <= 6145); larger: identity map
-    const int iper = K <= kIndexMaxK + 1 ? kIdxPer : K <= kIndexMaxKWide + 1 ? kIdxPerWide : 0;
-    const bool want_keys = poll_possible && iper;   // the index hashes the prep's fp32 keys
-    auto prof_end = [&]() {
-        if (!ctx->profile || (ts_a < 0 && ts_b < 0)) return;
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        mac_ctx::Prof p{ts_a, ts_na, ts_b, ts_nb, (int64_t)K, d_mode,
-                        ts_w >= 0 ? MAC_ALGO_POLL : tiled ? MAC_ALGO_TILED : MAC_ALGO_SCAN, ts_c, ts_nc,
-                        ts_f, ts_nf};
-        if (ts_c >= 0) {   // a poll chain: every launch's stamps by role (mac_profile_kernels)
-            const int64_t r[kRoleMask][2] = {{ts_c, ts_nc}, {ts_i, ts_ni}, {ts_s, ts_ns},
-                                                  {ts_w >= 0 ? -1 : ts_a, ts_w >= 0 ? 0 : ts_na},
-                                                  {ts_b, ts_nb}, {ts_g, ts_ng},
-                                                  {ts_w >= 0 ? -1 : ts_f, ts_w >= 0 ? 0 : ts_nf},
-                                                  {ts_w, ts_nw},
-                                                  {ts_w >= 0 ? ts_f : -1, ts_w >= 0 ? ts_nf : 0}};
+    uint64_t* ts_role(int role, int64_t nwg) { return take_ts(nwg, prof.role[role][0], prof.role[role][1]); }
+    uint64_t* ts_lone(int64_t nwg) { return take_ts(nwg, prof.a, prof.na); }
+    // (the five-launch chain's inner launches: only when its prep took its stamps)
+    uint64_t* ts_chain(int role, int64_t nwg) { return prof.role[kRolePrep][0] >= 0 ? ts_role(role, nwg) : nullptr; }
+
+    // The record of this call: the legacy fields from the roles (a: the walk launch mac_profile_read
+    // reads, b: the poll walk beside it, c / f: the chain's first and last launch). A chain whose
+    // prep took no stamps (the buffer was full) reports no role of its own.
+    void prof_end()
+    {
+        if (!ctx->profile) return;
+        auto& r = prof.role;
+        const bool fused = r[kRoleFiw][0] >= 0;
+        if (prof.a < 0) {
+            prof.a = r[fused ? kRoleFiw : kRoleTiledPoll][0];
+            prof.na = r[fused ? kRoleFiw : kRoleTiledPoll][1];
+        }
+        prof.b = r[kRolePoll][0];
+        prof.nb = r[kRolePoll][1];
+        if (prof.a < 0 && prof.b < 0) return;
+        prof.K = rq.K;
+        prof.mode = d_mode;
+        prof.algo = fused ? MAC_ALGO_POLL : rq.tiled ? MAC_ALGO_TILED : MAC_ALGO_SCAN;
+        prof.c = r[kRolePrep][0];
+        prof.nc = r[kRolePrep][1];
+        prof.f = r[fused ? kRoleFin2 : kRoleFin][0];
+        prof.nf = r[fused ? kRoleFin2 : kRoleFin][1];
+        if (prof.c < 0)
             for (int q = 0; q < kRoleMask; ++q) {
-                p.role[q][0] = r[q][0];
-                p.role[q][1] = r[q][1];
+                r[q][0] = -1;
+                r[q][1] = 0;
             }
-        }
-        p.role[kRoleMask][0] = ts_m;   // (with or without a poll chain)
-        p.role[kRoleMask][1] = ts_nm;
-        p.role[kRoleProgH][0] = ts_p;
-        p.role[kRoleProgH][1] = ts_np;
-        ctx->prof.push_back(p);
-    };
-
-    // a generated poll under swarm constraints (the native MADS driver): the mask launch first, one
-    // byte per candidate into the lane's buffer (reused stream-ordered), read by the prep launch
-    const uint8_t* d_mask8 = nullptr;
-    if (gcons && !src.cands && d_obj && K > 0) {
-        L->cmask.reserve((size_t)K);
-        d_mask8 = L->cmask.as<uint8_t>();
-        const int S = cons_slots(N);   // UAVs per thread: 1, 2, 4, 8 (N <= kConsMaxN, checked at begin)
-        uint64_t* tsm = take_ts(K, ts_m, ts_nm);
-        if (gmot) {   // ... and the motion constraints: with d_sep off, no sort and no LDS arrays
-            void (*const kern)(uint64_t*, CandSrc, int, ConsArgs, MotionArgs, uint8_t*) =
-                gcons->sep ? (S == 1 ? cons_mask_gen_motion_kernel<1, true> : S == 2 ? cons_mask_gen_motion_kernel<2, true>
-                            : S == 4 ? cons_mask_gen_motion_kernel<4, true> : cons_mask_gen_motion_kernel<8, true>)
-                           : (S == 1 ? cons_mask_gen_motion_kernel<1, false> : S == 2 ? cons_mask_gen_motion_kernel<2, false>
-                            : S == 4 ? cons_mask_gen_motion_kernel<4, false> : cons_mask_gen_motion_kernel<8, false>);
-            hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock),
-                               gcons->sep ? (uint32_t)(17 * kConsBlock * S) : 0u, s, tsm, src, N, *gcons, *gmot,
-                               L->cmask.as<uint8_t>());
-        } else {
-            void (*const kern)(uint64_t*, CandSrc, int, ConsArgs, uint8_t*) =
-                S == 1 ? cons_mask_gen_kernel<1> : S == 2 ? cons_mask_gen_kernel<2>
-              : S == 4 ? cons_mask_gen_kernel<4> : cons_mask_gen_kernel<8>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)K), dim3(kConsBlock), (uint32_t)(17 * kConsBlock * S), s, tsm,
-                               src, N, *gcons, L->cmask.as<uint8_t>());
-        }
-        HCK(hipGetLastError());
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        ctx->prof.push_back(prof);
     }
+};
 
-    // ... under progressive constraints (mac_mads_run_prog): h of every candidate, and the byte of a
-    // candidate the barrier drops (h NaN or above h_max) cleared beside the mask's
-    if (gprog && !src.cands && d_obj && K > 0) {
-        const int and_mask = d_mask8 ? 1 : 0;
-        L->cmask.reserve((size_t)K);
-        d_mask8 = L->cmask.as<uint8_t>();
-        uint64_t* tsp = take_ts(K, ts_p, ts_np);
-        hipLaunchKernelGGL(prog_h_kernel, dim3((unsigned)K), dim3(kProgBlock), 0, s, tsp, src, N, gprog->a,
-                           gprog->h_max, gprog->d_h, L->cmask.as<uint8_t>(), and_mask);
-        HCK(hipGetLastError());
-    }
-
-    CandSrc isrc = src;
-    // a generated poll on a mesh (mac_mads_mesh): the chains' launches are their own builds (kMesh)
-    const bool mesh = !src.cands && src.mesh() != nullptr;
-    const int target = 8 * ctx->cus;
-    const int G = (int)std::max<int64_t>(
-        1, std::min<int64_t>((target + K - 1) / K, std::max(1, N / kWavesPerBlock)));
-    const int64_t units = (int64_t)K * G;
-    // generated complete polls (the native MADS loop: K = 2n): the prep draws each B entry once
-    // for its plus and minus candidates (k_prep.h PrepArgs.pair)
-    // (n = the polled variables: 3N, or 2N for an xy-only poll)
-    const int npoll = src.polled(N);
-    const bool pair = !src.cands && src.k0 == 0 && K == 2 * npoll && npoll % 4 == 0 && kPrepC == 8;
-    // ... or, with one block of UAVs, prep_x_kernel's layout (k_prep.h prep_block_x<true>): a column
-    // triple of B per workgroup (its plus and minus candidates: 6), N workgroups, a ninth wave
-    // folding the penalty chains beside the keys and the records
-    // (full polls only: an xy-only poll takes prep_kernel)
-    const bool gen_x = !src.cands && !src.np && src.k0 == 0 && K == 6 * N && N >= 1 && N <= kPrepU;
-    const int nchain = pair ? npoll / 4 : (K + kPrepC - 1) / kPrepC;
-
-    // The fused chain (k_fiw.h: prep -> fiw -> fin2) whenever the poll walk runs on packed keys of at
-    // most kFwMaxK + 1 candidates, unless one of the context's last 64 polls did not suit it: a crowded
-    // poll (many shared entries: the five-launch chain's union pass), a scattered batch (the
-    // per-candidate walk) or escaped keys (fp32 keys). Either chain gives the same results. The
-    // history is long because a wrong choice costs asymmetrically: a crowded poll in the fused
-    // chain decides its shared entries per candidate in place (0.4-2 ms at configs 5 and 4
-    // clustered), an uncrowded one in the five-launch chain costs ~20 us more.
-    // A generated poll whose step the host knows (a stepper's, not the pipelined loop's) at
-    // 2^ell > 8 goes to the five-launch chain under AUTO: its disks spread over more than the
-    // index's direct-mapped box (ell <= 3) and its superset boxes overlap widely (config 5's first
-    // poll of an MPC step: 0.5 ms fused against ~0.11 ms).
-    const bool wide_gen = !src.cands && !src.mst &&
-                          (src.ltri ? (double)src.b * __builtin_fabs(src.delta) > 8.0 : src.b > 8);
-    if (poll_possible && want_keys && N > 0 && M > 0 && K > 0 && K <= kFwMaxK + 1 &&
-        ctx->chain != MAC_CHAIN_FIVE && walk_forced != kModeTiled &&
-        (ctx->chain == MAC_CHAIN_FUSED || (!wide_gen && !src.route_five))) {
-        ensure_hints(L);
-        volatile int* hw = (volatile int*)L->h_dc.p;
-        int bad_now = -1;   // the lane's last poll's report (a hint: it may be an older poll's)
-        if (L->last_chain == 2 && hw[8] >= 0) {
-            bad_now = hw[8] > kFwCrowdWork || hw[9] > 0 || hw[11] > 0 ? 1 : 0;   // (k_fiw.h kFwHints)
-            if (ctx->profile) {
-                const int64_t id = hw[9];
-                ctx->fw_reports.fetch_add(1, std::memory_order_relaxed);
-                ctx->fw_ident_sum.fetch_add(id, std::memory_order_relaxed);
-                if (id > ctx->fw_ident_max.load(std::memory_order_relaxed))
-                    ctx->fw_ident_max.store(id, std::memory_order_relaxed);
-            }
-        }
-        else if (L->last_chain == 1 && hw[0] < (1 << 30))
-            bad_now = hw[0] > kBitsMinDisks || hw[4] == kModeTiled ? 1 : 0;
-        if (bad_now >= 0) {
-            uint64_t o = ctx->fused_bad.load(std::memory_order_relaxed);
-            while (!ctx->fused_bad.compare_exchange_weak(o, (o << 1) | (uint64_t)bad_now,
-                                                         std::memory_order_relaxed)) {
-            }
-        }
-        const bool fused = ctx->fused_bad.load(std::memory_order_relaxed) == 0;
-        if (fused || ctx->chain == MAC_CHAIN_FUSED) {
-            const int ldk = keys_ld(K);
-            counts = ctx->w_uniform ? 1 : 0;
-            L->keysT.reserve(sizeof(float) * (size_t)4 * N * ldk);
-            // a matrix source: kPrepCX (+1) candidates per workgroup (k_prep.h prep_x_kernel)
-            const int gx = K / kPrepCX;
-            const bool xk = (src.cands && !pair && N <= kPrepU && gx >= 1 && K - gx * kPrepCX <= gx) || gen_x;
-            const int nprep = gen_x ? N : xk ? gx : nchain;
-            L->pd.reserve(sizeof(double4) * (size_t)nprep);
-            L->frows.reserve((counts ? sizeof(unsigned) : sizeof(double)) * (size_t)N * ldk);
-            if (L->fwhint.grow(sizeof(int) * kFwHints)) HCK(hipMemsetAsync(L->fwhint.p, 0, L->fwhint.cap, s));
-            // cons3 failures are left out of the walk when only objectives are asked for
-            const bool excl = d_obj && (d_prev || d_mask8) && !d_area && N <= kPrepU;
-            if (excl) L->dead8.reserve((size_t)ldk + 16);   // (the fused kernel reads 4-B words)
-            L->fwlist.reserve(sizeof(int4) * (size_t)std::max(N, kF2Pre));
-            if (L->fwcount.grow(sizeof(int))) HCK(hipMemsetAsync(L->fwcount.p, 0, L->fwcount.cap, s));
-            L->fwsxy.reserve(sizeof(double2) * (size_t)N * kFwShCap);
-            L->fwsw.reserve(sizeof(double) * (size_t)N * kFwShCap);
-            PrepArgs pr{};
-            pr.src = src;
-            pr.N = N;
-            pr.K = K;
-            pr.pa = pa;
-            pr.penalty = penalty;
-            pr.vp = d_vp;
-            pr.nchain = nprep;
-            pr.xbase = gx * kPrepCX;
-            pr.skip_failed = d_area ? 0 : 1;
-            pr.pair = pair ? 1 : 0;
-            pr.g = ctx->grid;
-            pr.keysP = L->keysT.as<uint32_t>();
-            pr.keysT = L->keysT.as<float>() + (size_t)N * ldk;
-            pr.ldk = ldk;
-            pr.pd = L->pd.as<double4>();
-            pr.dead8 = excl ? L->dead8.as<uint8_t>() : nullptr;
-            pr.mst_w = excl && d_prev && fb_mads ? fb_mads->st : nullptr;
-            pr.feas = d_feas;
-            pr.mask8 = d_mask8;
-            pr.lreset = L->fwcount.as<int>();
-            uint64_t* tsk = take_ts(nprep, ts_c, ts_nc);
-            using hclk = std::chrono::steady_clock;
-            hclk::time_point h1, h2, h3;
-            if (ctx->host_stats) h1 = hclk::now();
-            if (xk && gen_x)
-                hipLaunchKernelGGL((mesh ? prep_x_kernel<true, true> : prep_x_kernel<true>), dim3((unsigned)nprep),
-                                   dim3(kPrepU + kWave), 0, s, tsk, pr);
-            else if (xk)
-                hipLaunchKernelGGL(prep_x_kernel<false>, dim3((unsigned)nprep), dim3(kPrepU + kWave), 0, s, tsk, pr);
-            else
-                hipLaunchKernelGGL((mesh ? prep_kernel<true> : prep_kernel<false>), dim3((unsigned)nprep), dim3(kPrepU),
-                                   0, s, tsk, pr);
-            HCK(hipGetLastError());
-            if (ctx->host_stats) h2 = hclk::now();
-            FwArgs fa{};
-            fa.src = src;
-            fa.src.keysP = pr.keysP;
-            fa.src.keysT = pr.keysT;
-            fa.src.ldk = ldk;
-            fa.N = N;
-            fa.K = K;
-            fa.g = ctx->grid;
-            fa.dead = pr.dead8;
-            fa.pd = pr.pd;
-            fa.npd = nprep;
-            fa.xy = ctx->xys.as<double2>();
-            fa.w = ctx->ws.as<double>();
-            fa.off = ctx->off.as<int32_t>();
-            fa.counts = counts;
-            fa.crow = L->frows.as<unsigned>();
-            fa.frow = L->frows.as<double>();
-            fa.ldk = ldk;
-            fa.hint = L->fwhint.as<int>();
-            fa.sh = FwShared{L->fwcount.as<int>(), L->fwlist.as<int4>(), L->fwsxy.as<double2>(),
-                             L->fwsw.as<double>()};
-            const F2Shared f2s{fa.src, L->fwcount.as<int>(), L->fwlist.as<int4>(), L->fwsxy.as<double2>(),
-                               L->fwsw.as<double>(), fa.dead};
-            const unsigned nfw = 8 * (unsigned)((N + 7) / 8);
-            uint64_t* tsw = take_ts(nfw, ts_w, ts_nw);
-            ts_a = ts_w;   // (mac_profile_read: the walk launch)
-            ts_na = ts_nw;
-            // the source selects the instantiation of both launches (k_fiw.h kMat): a matrix poll's
-            // has no generator code in it; generated and basis-form polls take the other
-            const bool mat = src.cands != nullptr;
-            const auto fiw_kern =
-                counts ? (mat ? fiw_kernel<true, true> : mesh ? fiw_kernel<true, false, true> : fiw_kernel<true, false>)
-                       : (mat ? fiw_kernel<false, true> : mesh ? fiw_kernel<false, false, true> : fiw_kernel<false, false>);
-            hipLaunchKernelGGL(fiw_kern, dim3(nfw), dim3(kFwThreads), 0, s, tsw, fa);
-            HCK(hipGetLastError());
-            if (ctx->host_stats) h3 = hclk::now();
-            const unsigned nfin = 8 * (unsigned)((K + 8 * kF2C - 1) / (8 * kF2C));
-            FinBest fb{};
-            if (d_best) {
-                L->finblk.reserve(2 * sizeof(unsigned long long) * nfin);
-                if (L->finarrive.grow(sizeof(unsigned)))
-                    HCK(hipMemsetAsync(L->finarrive.p, 0, L->finarrive.cap, s));
-                if (fb_mads) fb = *fb_mads;
-                fb.best = d_best;
-                fb.mirror = d_mirror;
-                fb.seq = mirror_seq;
-                fb.idx_base = idx_base;
-                fb.blk = L->finblk.as<unsigned long long>();
-                fb.arrive = L->finarrive.as<unsigned>();
-                fb.hint = L->fwhint.as<int>();   // (read and cleared by the argmin's last block)
-                fb.hint_host = L->d_dc + 8;
-                fb.nhint = kFwHints;
-                fb.feas = d_mirror ? d_feas : nullptr;
-            }
-            uint64_t* tsf = take_ts(nfin, ts_f, ts_nf);
-            // (fb.np: the pipelined loop's update of an xy-only poll, a generated source)
-            const bool xy = fb.np != 0 && !mat;
-            // (... and on a mesh: the builds with the scaled values and update)
-            const bool fm = mesh;
-            const auto fin2_kern =
-                counts ? (mat ? fin2_kernel<true, true>
-                          : fm ? (xy ? fin2_kernel<true, false, true, true> : fin2_kernel<true, false, false, true>)
-                          : xy ? fin2_kernel<true, false, true> : fin2_kernel<true, false>)
-                       : (mat ? fin2_kernel<false, true>
-                          : fm ? (xy ? fin2_kernel<false, false, true, true> : fin2_kernel<false, false, false, true>)
-                          : xy ? fin2_kernel<false, false, true> : fin2_kernel<false, false>);
-            hipLaunchKernelGGL(fin2_kern, dim3(nfin), dim3(kF2Threads), 0, s,
-                               counts ? L->frows.as<unsigned>() : nullptr, counts ? nullptr : L->frows.as<double>(),
-                               ldk, N, K, ctx->w0, d_vp, d_area, d_obj, fb, f2s, tsf);
-            HCK(hipGetLastError());
-            if (ctx->host_stats) {
-                const auto h4 = hclk::now();
-                std::lock_guard<std::mutex> lk(ctx->mu);
-                ctx->hs_t[0] += std::chrono::duration<double>(h1 - t_poll_entry).count();
-                ctx->hs_t[1] += std::chrono::duration<double>(h2 - h1).count();
-                ctx->hs_t[2] += std::chrono::duration<double>(h3 - h2).count();
-                ctx->hs_t[3] += std::chrono::duration<double>(h4 - h3).count();
-                ++ctx->hs_n;
-            }
-            L->last_chain = 2;
-            prof_end();
-            return;
-        }
-    }
-    if (poll_possible) L->last_chain = 1;
-    int nrec = nchain;   // the prep's records per disk (workgroups of the prep launch)
-
-    if ((d_obj || poll_possible) && K > 0) {
-        // the prep launch (k_prep.h): penalty chains + cons3 into vp, the poll walk's partial
-        // regions, and the index's fp32 keys
-        // a generated complete poll with the index's keys: prep_x_kernel's column-triple layout
-        const bool gx5 = gen_x && poll_possible && want_keys;
-        nrec = gx5 ? N : nchain;
-        PrepArgs pr{};
-        pr.src = src;
-        pr.N = N;
-        pr.K = K;
-        pr.pa = pa;
-        pr.penalty = penalty;
-        pr.vp = d_vp;
-        pr.nchain = nrec;
-        pr.skip_failed = d_area ? 0 : 1;   // (the index maps them to an inert position likewise)
-        pr.pair = pair ? 1 : 0;
-        pr.g = ctx->grid;
-        pr.feas = d_feas;
-        pr.mask8 = d_mask8;
-        // the pipelined MADS loop: a poll cons3 rejects whole is decided by the prep (k_prep.h
-        // MadsState.skip) when its failures are left out of the walk (the prep's excl)
-        pr.mst_w = fb_mads && poll_possible && d_obj && d_prev && !d_area && N <= kPrepU ? fb_mads->st
-                                                                                           : nullptr;
-        if (poll_possible) {
-            L->prec.reserve(sizeof(int4) * (size_t)nrec * N);
-            pr.prec = L->prec.as<int4>();
-        }
-        if (want_keys) {
-            const int ldk = keys_ld(K);
-            // packed keys (one row per disk), then the fp32 rows of escaped values (k_prep.h)
-            L->keysT.reserve(sizeof(float) * (size_t)4 * N * ldk);
-            pr.keysP = L->keysT.as<uint32_t>();
-            pr.keysT = L->keysT.as<float>() + (size_t)N * ldk;
-            pr.ldk = ldk;
-            isrc.keysP = pr.keysP;
-            isrc.keysT = pr.keysT;
-            isrc.ldk = ldk;
-        }
-        uint64_t* tsk = poll_possible ? take_ts(nrec, ts_c, ts_nc) : nullptr;
-        if (gx5)
-            hipLaunchKernelGGL((mesh ? prep_x_kernel<true, true> : prep_x_kernel<true>), dim3((unsigned)nrec),
-                               dim3(kPrepU + kWave), 0, s, tsk, pr);
+// A generated poll of the native MADS driver under swarm constraints: the mask launch first, one
+// byte per candidate into the lane's buffer (reused stream-ordered), read by the prep launch. Under
+// progressive constraints (mac_mads_run_prog): h of every candidate, and the byte of a candidate the
+// barrier drops (h NaN or above h_max) cleared beside the mask's.
+static void enqueue_gen_masks(EvalRun& r)
+{
+    const EvalReq& rq = r.rq;
+    const int N = rq.N, K = rq.K;
+    r.L->cmask.reserve((size_t)K);
+    uint8_t* d_mask = r.L->cmask.as<uint8_t>();
+    if (rq.cons) {
+        const int S = cons_slots(N);   // (N <= kConsMaxN, checked at begin)
+        uint64_t* tsm = r.ts_role(kRoleMask, K);
+        if (rq.motion)
+            hipLaunchKernelGGL(mask_gen_motion_kern(S, rq.cons->sep), dim3((unsigned)K), dim3(kConsBlock),
+                               rq.cons->sep ? mask_lds(S) : 0u, r.s, tsm, rq.src, N, *rq.cons, *rq.motion, d_mask);
         else
-            hipLaunchKernelGGL((mesh ? prep_kernel<true> : prep_kernel<false>), dim3((unsigned)nchain), dim3(kPrepU), 0,
-                               s, tsk, pr);
+            hipLaunchKernelGGL(mask_gen_kern(S), dim3((unsigned)K), dim3(kConsBlock), mask_lds(S), r.s, tsm, rq.src,
+                               N, *rq.cons, d_mask);
         HCK(hipGetLastError());
     }
+    if (rq.prog) {
+        uint64_t* tsp = r.ts_role(kRoleProgH, K);
+        hipLaunchKernelGGL(prog_h_kernel, dim3((unsigned)K), dim3(kProgBlock), 0, r.s, tsp, rq.src, N, rq.prog->a,
+                           rq.prog->h_max, rq.prog->d_h, d_mask, rq.cons ? 1 : 0);
+        HCK(hipGetLastError());
+    }
+    r.d_mask8 = d_mask;
+}
 
-    if (N == 0 || M == 0) {  // no UAV or no entry: every area is 0 (the loops never run)
-        L->partial.reserve(sizeof(double) * (size_t)K);
-        HCK(hipMemsetAsync(L->partial.p, 0, sizeof(double) * (size_t)K, s));
-    } else if (!tiled) {
-        L->disks.reserve(sizeof(DiskRec) * (size_t)N * K);
-        hipLaunchKernelGGL(disk_prep_kernel, dim3(grid1d((int64_t)N * K, 256)), dim3(256), 0, s,
-                           src, N, K, L->disks.as<DiskRec>());
-        HCK(hipGetLastError());
-        constexpr int KB = 4, PPT = 4;
-        const int64_t per_pass = (int64_t)kBlock * PPT;
-        int64_t nblk = std::max<int64_t>(1, (M + per_pass - 1) / per_pass);
-        const int kgroups = (K + KB - 1) / KB;
-        const int64_t want = std::max<int64_t>(1, (int64_t)(8 * ctx->cus) / kgroups);
-        nblk = std::min(nblk, want);
-        int64_t chunk = (M + nblk - 1) / nblk;
-        chunk = ((chunk + per_pass - 1) / per_pass) * per_pass;
-        nblk = std::max<int64_t>(1, (M + chunk - 1) / chunk);
-        n_other = (int)nblk;
-        L->partial.reserve(sizeof(double) * (size_t)K * nblk);
-        uint64_t* ts = take_ts(nblk * kgroups, ts_a, ts_na);
-        hipLaunchKernelGGL((coverage_scan_kernel<KB, PPT>), dim3((unsigned)nblk, (unsigned)kgroups),
-                           dim3(kBlock), 0, s, ts, ctx->xys.as<double2>(), ctx->ws.as<double>(), M,
-                           L->disks.as<DiskRec>(), N, K, chunk, L->partial.as<double>());
-        HCK(hipGetLastError());
-    } else {
-        // the disk index: distinct disks per UAV, their records, the map and the poll walk's lane
-        // constants (k_index.h)
-        L->disks.reserve(sizeof(DiskRec) * (size_t)N * K);
-        L->umap.reserve(sizeof(int) * (size_t)N * K);
-        L->ucount.reserve(sizeof(int) * (size_t)N);
-        if (poll_possible) {  // the poll walk's lane constants and row descriptors
-            L->lane4.reserve(sizeof(float4) * (size_t)N * K);
-            L->lanexp.reserve(sizeof(float) * (size_t)N * K);
-            L->rows.reserve(sizeof(int2) * (size_t)N * (kRowInfo + 1));
-        }
-        counts = poll_possible && ctx->w_uniform ? 1 : 0;   // equal weights: the walks count
-        n_other = G;
-        const DiskRec* d_urec = L->disks.as<DiskRec>();
-        const int* d_map = L->umap.as<int>();
-        if (!poll_possible) {
-            // the per-candidate walk alone (small batches, the single-candidate closure): the
-            // identity map, one thread per (disk, candidate), no key pass
-            const int64_t nk = (int64_t)N * K;
-            hipLaunchKernelGGL(disk_index_identity_kernel, dim3(grid1d(nk, 256)), dim3(256), 0, s,
-                               src, N, K, L->disks.as<DiskRec>(), L->umap.as<int>());
-            HCK(hipGetLastError());
-            L->partial.reserve(sizeof(double) * (size_t)K * G);
-            uint64_t* ts = take_ts(units, ts_a, ts_na);
-            hipLaunchKernelGGL(coverage_tiled_kernel, dim3((unsigned)units), dim3(kBlock),
-                               (uint32_t)tiled_lds_bytes(N), s, ts, ctx->xys.as<double2>(),
-                               ctx->ws.as<double>(), ctx->off.as<int32_t>(), ctx->grid, d_urec, d_map,
-                               N, K, G, nullptr, L->partial.as<double>());
-            HCK(hipGetLastError());
-        } else {
-            L->region.reserve(sizeof(int4) * N);
-            L->cost.reserve(sizeof(double2) * N);
-            L->mode.reserve((1 + kDcCount) * sizeof(int));  // [0] walk, [1..kDcCount] the poll walk's counters (k_common.h)
-            const IndexOut io{L->disks.as<DiskRec>(), L->umap.as<int>(), L->ucount.as<int>(),
-                              L->region.as<int4>(), L->cost.as<double2>(), L->mode.as<int>() + 1,
-                              L->prec.as<int4>(), nrec,
-                              L->lane4.as<float4>(), L->lanexp.as<float>(), L->rows.as<int2>(),
-                              ctx->off.as<int32_t>(),
-                              // cons3 failures are not evaluated (objective +inf) unless the caller
-                              // also wants every candidate's area
-                              d_area ? nullptr : d_vp};
-            const unsigned nidx = 8 * ((N + 7) / 8);
-            const int dedup = iper ? 1 : 0;
-            uint64_t* tsi = ts_c >= 0 ? take_ts(nidx, ts_i, ts_ni) : nullptr;
-            // (an xy-only poll's kernels are their own instantiations: the full poll's stay as they were)
-            if (mesh) {   // (... and a mesh's likewise)
-                using IdxKern = void (*)(uint64_t*, CandSrc, int, int, Grid, int, IndexOut);
-                const bool wide = iper == kIdxPerWide, keys = isrc.keysT != nullptr;
-                const IdxKern kern =
-                    isrc.np ? (keys ? (wide ? disk_index_kernel<true, kIdxPerWide, true, true> : disk_index_kernel<true, kIdxPer, true, true>)
-                                    : (wide ? disk_index_kernel<false, kIdxPerWide, true, true> : disk_index_kernel<false, kIdxPer, true, true>))
-                            : (keys ? (wide ? disk_index_kernel<true, kIdxPerWide, false, true> : disk_index_kernel<true, kIdxPer, false, true>)
-                                    : (wide ? disk_index_kernel<false, kIdxPerWide, false, true> : disk_index_kernel<false, kIdxPer, false, true>));
-                hipLaunchKernelGGL(kern, dim3(nidx), dim3(kIdxThreads), 0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            } else if (isrc.np && isrc.keysT && iper == kIdxPerWide)
-                hipLaunchKernelGGL((disk_index_kernel<true, kIdxPerWide, true>), dim3(nidx), dim3(kIdxThreads),
-                                   0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            else if (isrc.np && isrc.keysT)
-                hipLaunchKernelGGL((disk_index_kernel<true, kIdxPer, true>), dim3(nidx), dim3(kIdxThreads), 0, s,
-                                   tsi, isrc, N, K, ctx->grid, dedup, io);
-            else if (isrc.np && iper == kIdxPerWide)
-                hipLaunchKernelGGL((disk_index_kernel<false, kIdxPerWide, true>), dim3(nidx), dim3(kIdxThreads),
-                                   0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            else if (isrc.np)
-                hipLaunchKernelGGL((disk_index_kernel<false, kIdxPer, true>), dim3(nidx), dim3(kIdxThreads), 0,
-                                   s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            else if (isrc.keysT && iper == kIdxPerWide)
-                hipLaunchKernelGGL((disk_index_kernel<true, kIdxPerWide>), dim3(nidx), dim3(kIdxThreads),
-                                   0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            else if (isrc.keysT)
-                hipLaunchKernelGGL((disk_index_kernel<true, kIdxPer>), dim3(nidx), dim3(kIdxThreads), 0, s,
-                                   tsi, isrc, N, K, ctx->grid, dedup, io);
-            else if (iper == kIdxPerWide)
-                hipLaunchKernelGGL((disk_index_kernel<false, kIdxPerWide>), dim3(nidx), dim3(kIdxThreads),
-                                   0, s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            else
-                hipLaunchKernelGGL((disk_index_kernel<false, kIdxPer>), dim3(nidx), dim3(kIdxThreads), 0,
-                                   s, tsi, isrc, N, K, ctx->grid, dedup, io);
-            HCK(hipGetLastError());
-            // launch hints from the lane's previous polls (mapped host memory the poll kernel
-            // writes): disks with neighbours, most positions of a disk, the walk AUTO would choose
-            ensure_hints(L);
-            // neighbour lists (k_walk.h walk_setup_kernel), then — when the per-candidate walk is
-            // forced, or AUTO chose it on one of the lane's last 8 polls — the walk choice and that
-            // walk (coverage_tiled_poll_kernel). Otherwise the poll walk runs; its kernel records
-            // the choice AUTO would have made, so a batch that favours the per-candidate walk gets
-            // it from the lane's next poll on (the choice only changes speed, never results).
-            // (a lane's first poll has no report yet: it launches the kernel once, and the
-            // sentinel stays out of the history)
-            const int walk_now = ((volatile int*)L->h_dc.p)[4];
-            bool hinted = walk_now == 0;
-            if (!hinted) {
-                for (int q = 7; q > 0; --q) L->walk_hist[q] = L->walk_hist[q - 1];
-                L->walk_hist[0] = walk_now;
-            }
-            for (int q = 0; q < 8; ++q) hinted |= L->walk_hist[q] == kModeTiled;
-            const bool run_tiled = walk_forced == kModeTiled || (walk_forced == 0 && hinted);
-            L->nbr.reserve(sizeof(uint16_t) * (size_t)N * kPollNbr);
-            L->ncount.reserve(sizeof(int) * (size_t)N);
-            L->dlist.reserve(sizeof(int) * (size_t)N);
-            L->qual.reserve(sizeof(int) * (size_t)N);
-            L->nboxT.reserve(sizeof(int4) * (size_t)N * kPollNbr);
-            L->partial.reserve(sizeof(double) * (size_t)K * std::max(G, N));
-            // the shared-entry pass of crowded polls, launched when one of the lane's last 8 polls
-            // had more than kBitsMinDisks disks with neighbours (the poll kernel writes the count to
-            // mapped host memory): a hint only, the poll kernel takes every disk when it is not
-            // launched (MADS alternates crowded and quiet polls, and a crowded poll without the
-            // pass costs several times its launch)
-            const int dc_now = *(volatile int*)L->h_dc.p;   // 1 << 30 until a poll wrote it
-            int dc_max = dc_now;
-            if (dc_now < (1 << 30)) {
-                for (int q = 7; q > 0; --q) L->dc_hist[q] = L->dc_hist[q - 1];
-                L->dc_hist[0] = dc_now;
-                for (int q = 0; q < 8; ++q) dc_max = std::max(dc_max, L->dc_hist[q]);
-            }
-            // 0: fp64 jobs; 1: above kBitsMinDisks disks with neighbours; 2: always
-            bits_on = ctx->shared_mode == MAC_SHARED_BITS ? 2
-                    : ctx->shared_mode == MAC_SHARED_FP64 ? 0
-                    : dc_max > kBitsMinDisks ? 1 : 0;
-            // Both passes stage an entry as its fp32 offset (u, v) from a region's centre with
-            // q = u u + v v, and q = +inf marks "no entry" (k_or.h, k_bits.h: outside the box, past
-            // the list, non-finite). A finite entry must therefore keep q finite: |u|, |v| below
-            // 2^63. Offsets are bounded by the grid's extent, so on a grid of 2^62 or more (a far
-            // outlier sets the pitch: the centre of the tile that holds the rest of the list lies
-            // S / 2 away from it) finite entries would drop out of the unions, and the poll
-            // kernel's fp64 jobs take every disk there.
-            const Grid& gr = ctx->grid;
-            if (!(((double)std::max(gr.nTx, gr.nTy) + 1.0) * gr.S < 0x1p62)) bits_on = 0;
-            // equal weights: the union pass (k_or.h), whose jobs walk_setup lists with the upper
-            // neighbour boxes; weighted lists: the bit-word kernel (k_bits.h)
-            OrSetup orj{};
-            if (bits_on && counts) {
-                L->nboxU.reserve(sizeof(int4) * (size_t)N * kPollNbr);
-                L->ncountU.reserve(sizeof(int) * (size_t)N);
-                const int64_t cap = M / kOrE + N + 64;   // the owned sets are disjoint
-                L->orjobs.reserve(sizeof(int2) * (size_t)cap * kOrBuckets);   // a list per bucket
-                orj = OrSetup{L->nboxU.as<int4>(), L->ncountU.as<int>(), L->orjobs.as<int2>(), (int)cap,
-                              ctx->off.as<int32_t>(), ctx->grid, L->ucount.as<int>()};
-            }
-            uint64_t* tss = ts_c >= 0 ? take_ts(N, ts_s, ts_ns) : nullptr;
-            hipLaunchKernelGGL(walk_setup_kernel, dim3((unsigned)N), dim3(kBlock), 0, s, tss, N,
-                               L->region.as<int4>(), L->nbr.as<uint16_t>(), L->nboxT.as<int4>(),
-                               L->ncount.as<int>(), L->dlist.as<int>(), L->mode.as<int>() + 1,
-                               L->mode.as<int>(), L->qual.as<int>(), src.mst, orj);
-            HCK(hipGetLastError());
-            if (run_tiled) {
-                // one workgroup per CU at most, grid-striding over the (candidate, slice) units
-                const unsigned nwg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(units, ctx->cus));
-                uint64_t* ts = take_ts(nwg, ts_a, ts_na);
-                hipLaunchKernelGGL(coverage_tiled_poll_kernel, dim3(nwg), dim3(kBlock),
-                                   (uint32_t)tiled_lds_bytes(N), s, ts, ctx->xys.as<double2>(),
-                                   ctx->ws.as<double>(), ctx->off.as<int32_t>(), ctx->grid, d_urec, d_map,
-                                   N, K, G, L->mode.as<int>(), L->partial.as<double>(),
-                                   L->nbr.as<uint16_t>(), L->ncount.as<int>(), L->cost.as<double2>(),
-                                   kPollCostRatio, walk_forced, L->d_dc + 4);
-                HCK(hipGetLastError());
-            }
-            d_mode = L->mode.as<int>();
-            d_umap = d_map;
-        }
-        if (poll_possible) {
-            // walk rows: the lane's last 8 polls' most distinct positions of a disk (poll kernel
-            // hint), one row per kPollKPB-position slice up to 4 (further slices loop)
-            const int um_now = ((volatile int*)L->h_dc.p)[2];
-            for (int q = 7; q > 0; --q) L->um_hist[q] = L->um_hist[q - 1];
-            L->um_hist[0] = um_now;
-            int um_max = 0;
-            for (int q = 0; q < 8; ++q) um_max = std::max(um_max, L->um_hist[q]);
-            const int gy = std::max(1, std::min(4, (um_max + kPollKPB - 1) / kPollKPB));
-            L->spart.reserve(sizeof(double) * (size_t)N * K);
-            const int n_shared = kSharedWG;
-            const dim3 pgrid(8 * ((N + 7) / 8) + n_shared, gy);   // walk workgroups, then shared
-            uint64_t* ts = take_ts((int64_t)pgrid.x * pgrid.y, ts_b, ts_nb);
-            hipLaunchKernelGGL(coverage_poll_kernel, pgrid, dim3(kPollThreads), 0, s, ts,
-                               ctx->xys.as<double2>(), ctx->ws.as<double>(),
-                               ctx->off.as<int32_t>(), ctx->grid, d_urec, d_map,
-                               L->ucount.as<int>(), L->region.as<int4>(), L->nbr.as<uint16_t>(),
-                               L->nboxT.as<int4>(), L->lane4.as<float4>(), L->lanexp.as<float>(),
-                               L->rows.as<int2>(),
-                               L->ncount.as<int>(), L->dlist.as<int>(), L->mode.as<int>() + 1,
-                               L->mode.as<int>() + 2, N, K,
-                               d_mode, L->partial.as<double>(), L->spart.as<double>(), n_shared, counts,
-                               bits_on, L->d_dc, L->qual.as<int>(),
-                               walk_forced == 0 ? L->cost.as<double2>() : nullptr, kPollCostRatio);
-            HCK(hipGetLastError());
-            // the shared entries of crowded polls: the union pass (equal weights, k_or.h) or
-            // bit-words per distinct position (k_bits.h); both return at once when few disks have
-            // neighbours (the poll kernel took them)
-            const unsigned nbits = (unsigned)std::max(1, std::min(N, ctx->cus));
-            const unsigned nor = (unsigned)(2 * ctx->cus);   // grid-strides over the listed jobs
-            uint64_t* tsg = bits_on && ts_c >= 0 ? take_ts(counts ? nor : nbits, ts_g, ts_ng) : nullptr;
-            if (!bits_on)
-                ;
-            else if (counts) {
-                OrArgs oa{};
-                oa.xy = ctx->xys.as<double2>();
-                oa.off = ctx->off.as<int32_t>();
-                oa.g = ctx->grid;
-                oa.urec = d_urec;
-                oa.umap = d_map;
-                oa.ucount = L->ucount.as<int>();
-                oa.region = L->region.as<int4>();
-                oa.nbrT = L->nbr.as<uint16_t>();
-                oa.nboxT = L->nboxT.as<int4>();
-                oa.ncount = L->ncount.as<int>();
-                oa.nboxU = L->nboxU.as<int4>();
-                oa.ncountU = L->ncountU.as<int>();
-                oa.lane4 = L->lane4.as<float4>();
-                oa.lanexp = L->lanexp.as<float>();
-                oa.jobs = L->orjobs.as<int2>();
-                oa.dcount = L->mode.as<int>() + 1;
-                oa.mode = d_mode;
-                oa.spart = L->spart.as<unsigned>();
-                oa.N = N;
-                oa.K = K;
-                oa.bits_on = bits_on;
-                oa.cap = (int)(M / kOrE + N + 64);
-                hipLaunchKernelGGL(shared_or_kernel, dim3(nor), dim3(kOrThreads), 0, s, tsg, oa);
-            } else
-                hipLaunchKernelGGL(shared_bits_kernel<false>, dim3(nbits), dim3(kBitsThreads), 0, s,
-                                   tsg, ctx->xys.as<double2>(), ctx->ws.as<double>(), ctx->off.as<int32_t>(),
-                                   ctx->grid, d_urec, d_map, L->ucount.as<int>(), L->region.as<int4>(),
-                                   L->nbr.as<uint16_t>(), L->lane4.as<float4>(), L->lanexp.as<float>(),
-                                   L->ncount.as<int>(), L->qual.as<int>(), L->mode.as<int>() + 1, d_mode,
-                                   N, K, L->spart.as<double>(), bits_on == 2 ? 0 : kBitsMinDisks);
-            HCK(hipGetLastError());
-            d_spart = L->spart.as<double>();
-            d_ncount = L->ncount.as<int>();
+// The fused chain's turn under AUTO: the lane's last poll's report goes into the context's history,
+// and the chain runs unless one of the last 64 reported polls did not suit it: a crowded poll (many
+// shared entries: the five-launch chain's union pass), a scattered batch (the per-candidate walk) or
+// escaped keys (fp32 keys). Either chain gives the same results. The history is long because a
+// wrong choice costs asymmetrically: a crowded poll in the fused chain decides its shared entries
+// per candidate in place (0.4-2 ms at configs 5 and 4 clustered), an uncrowded one in the
+// five-launch chain costs ~20 us more.
+static bool fused_history_allows(mac_ctx* ctx, Lane* L)
+{
+    ensure_hints(L);
+    volatile int* hw = (volatile int*)L->h_dc.p;
+    int bad_now = -1;   // the lane's last poll's report (a hint: it may be an older poll's)
+    if (L->last_chain == 2 && hw[8] >= 0) {
+        bad_now = hw[8] > kFwCrowdWork || hw[9] > 0 || hw[11] > 0 ? 1 : 0;   // (k_fiw.h kFwHints)
+        if (ctx->profile) {
+            const int64_t id = hw[9];
+            ctx->fw_reports.fetch_add(1, std::memory_order_relaxed);
+            ctx->fw_ident_sum.fetch_add(id, std::memory_order_relaxed);
+            if (id > ctx->fw_ident_max.load(std::memory_order_relaxed))
+                ctx->fw_ident_max.store(id, std::memory_order_relaxed);
         }
     }
-    // finalize, with the poll argmin taken by its last-arriving block (k_final.h)
-    const unsigned nfin = 8 * (unsigned)((K + 8 * kFinC - 1) / (8 * kFinC));   // k_final.h: XCD map
+    else if (L->last_chain == 1 && hw[0] < (1 << 30))
+        bad_now = hw[0] > kBitsMinDisks || hw[4] == kModeTiled ? 1 : 0;
+    if (bad_now >= 0) {
+        uint64_t o = ctx->fused_bad.load(std::memory_order_relaxed);
+        while (!ctx->fused_bad.compare_exchange_weak(o, (o << 1) | (uint64_t)bad_now,
+                                                     std::memory_order_relaxed)) {
+        }
+    }
+    return ctx->fused_bad.load(std::memory_order_relaxed) == 0;
+}
+
+// The key rows of a poll in the lane's buffer: packed keys (one row per disk), then the fp32 rows
+// of escaped values (k_prep.h); `src` is the source the launches after the prep read them through.
+static void key_rows(Lane* L, int N, int K, PrepArgs& pr, CandSrc& src)
+{
+    const int ldk = keys_ld(K);
+    L->keysT.reserve(sizeof(float) * (size_t)4 * N * ldk);
+    pr.keysP = L->keysT.as<uint32_t>();
+    pr.keysT = L->keysT.as<float>() + (size_t)N * ldk;
+    pr.ldk = ldk;
+    src.keysP = pr.keysP;
+    src.keysT = pr.keysT;
+    src.ldk = ldk;
+}
+
+// The prep launch's arguments (k_prep.h: penalty chains + cons3 into vp, the walks' records, the
+// index's keys) but the chain's own (prec; xbase, pd, dead8, lreset); nwg: its workgroups.
+static PrepArgs prep_args(const EvalRun& r, int nwg, CandSrc& keyed)
+{
+    const EvalReq& rq = r.rq;
+    PrepArgs pr{};
+    pr.src = rq.src;
+    pr.N = rq.N;
+    pr.K = rq.K;
+    pr.pa = PenArgs{rq.d_rmax, rq.d_prev, rq.d_dlimT, rq.d_dlim_raw, rq.tan_half_fov};
+    pr.penalty = rq.penalty;
+    pr.vp = r.d_vp;
+    pr.nchain = nwg;
+    pr.skip_failed = rq.d_area ? 0 : 1;   // (the index maps them to an inert position likewise)
+    pr.pair = r.pl.pair ? 1 : 0;
+    pr.g = r.ctx->grid;
+    pr.feas = rq.d_feas;
+    pr.mask8 = r.d_mask8;
+    // the pipelined MADS loop: a poll cons3 rejects whole is decided by the prep (k_prep.h
+    // MadsState.skip) when its failures are left out of the walk
+    pr.mst_w = rq.fb_mads && r.pl.poll_possible && r.pl.excl && rq.d_prev ? rq.fb_mads->st : nullptr;
+    if (r.pl.want_keys) key_rows(r.L, rq.N, rq.K, pr, keyed);
+    return pr;
+}
+
+// The argmin's arguments of the chain's last launch (k_final.h: taken by its last-arriving block of
+// nfin); all zero without d_best.
+static FinBest fin_best(const EvalRun& r, unsigned nfin)
+{
+    const EvalReq& rq = r.rq;
+    Lane* L = r.L;
     FinBest fb{};
-    if (d_best) {
-        L->finblk.reserve(2 * sizeof(unsigned long long) * nfin);
-        if (L->finarrive.grow(sizeof(unsigned)))   // zero once; the last block of each launch resets it
-            HCK(hipMemsetAsync(L->finarrive.p, 0, L->finarrive.cap, s));
-        if (fb_mads) fb = *fb_mads;   // the pipelined MADS loop's update fields
-        fb.best = d_best;
-        fb.mirror = d_mirror;
-        fb.seq = mirror_seq;
-        fb.idx_base = idx_base;
-        fb.blk = L->finblk.as<unsigned long long>();
-        fb.arrive = L->finarrive.as<unsigned>();
-        fb.feas = d_mirror ? d_feas : nullptr;
+    if (!rq.d_best) return fb;
+    L->finblk.reserve(2 * sizeof(unsigned long long) * nfin);
+    if (L->finarrive.grow(sizeof(unsigned)))   // zero once; the last block of each launch resets it
+        HCK(hipMemsetAsync(L->finarrive.p, 0, L->finarrive.cap, r.s));
+    if (rq.fb_mads) fb = *rq.fb_mads;   // the pipelined MADS loop's update fields
+    fb.best = rq.d_best;
+    fb.mirror = rq.d_mirror;
+    fb.seq = rq.mirror_seq;
+    fb.idx_base = rq.idx_base;
+    fb.blk = L->finblk.as<unsigned long long>();
+    fb.arrive = L->finarrive.as<unsigned>();
+    fb.feas = rq.d_mirror ? rq.d_feas : nullptr;
+    return fb;
+}
+
+// The fused chain (k_fiw.h): prep -> fiw_kernel -> fin2_kernel.
+static void enqueue_fused(EvalRun& r)
+{
+    const EvalReq& rq = r.rq;
+    const EvalPlan& pl = r.pl;
+    mac_ctx* ctx = r.ctx;
+    Lane* L = r.L;
+    hipStream_t s = r.s;
+    const int N = rq.N, K = rq.K, counts = pl.counts;
+    const bool mat = rq.src.cands != nullptr;
+    FwArgs fa{};
+    fa.src = rq.src;
+    PrepArgs pr = prep_args(r, pl.nprep, fa.src);
+    const int ldk = pr.ldk;
+    L->pd.reserve(sizeof(double4) * (size_t)pl.nprep);
+    L->frows.reserve((counts ? sizeof(unsigned) : sizeof(double)) * (size_t)N * ldk);
+    if (L->fwhint.grow(sizeof(int) * kFwHints)) HCK(hipMemsetAsync(L->fwhint.p, 0, L->fwhint.cap, s));
+    if (pl.excl) L->dead8.reserve((size_t)ldk + 16);   // (the fused kernel reads 4-B words)
+    L->fwlist.reserve(sizeof(int4) * (size_t)std::max(N, kF2Pre));
+    if (L->fwcount.grow(sizeof(int))) HCK(hipMemsetAsync(L->fwcount.p, 0, L->fwcount.cap, s));
+    L->fwsxy.reserve(sizeof(double2) * (size_t)N * kFwShCap);
+    L->fwsw.reserve(sizeof(double) * (size_t)N * kFwShCap);
+    pr.xbase = pl.xbase;
+    pr.pd = L->pd.as<double4>();
+    pr.dead8 = pl.excl ? L->dead8.as<uint8_t>() : nullptr;
+    pr.lreset = L->fwcount.as<int>();
+    uint64_t* tsk = r.ts_role(kRolePrep, pl.nprep);
+    using hclk = std::chrono::steady_clock;
+    hclk::time_point h1, h2, h3;
+    if (ctx->host_stats) h1 = hclk::now();
+    hipLaunchKernelGGL(prep_kern(pl.prep_fused, pl.mesh), dim3((unsigned)pl.nprep), prep_block(pl.prep_fused), 0, s,
+                       tsk, pr);
+    HCK(hipGetLastError());
+    if (ctx->host_stats) h2 = hclk::now();
+    fa.N = N;
+    fa.K = K;
+    fa.g = ctx->grid;
+    fa.dead = pr.dead8;
+    fa.pd = pr.pd;
+    fa.npd = pl.nprep;
+    fa.xy = ctx->xys.as<double2>();
+    fa.w = ctx->ws.as<double>();
+    fa.off = ctx->off.as<int32_t>();
+    fa.counts = counts;
+    fa.crow = L->frows.as<unsigned>();
+    fa.frow = L->frows.as<double>();
+    fa.ldk = ldk;
+    fa.hint = L->fwhint.as<int>();
+    fa.sh = FwShared{L->fwcount.as<int>(), L->fwlist.as<int4>(), L->fwsxy.as<double2>(), L->fwsw.as<double>()};
+    const F2Shared f2s{fa.src, L->fwcount.as<int>(), L->fwlist.as<int4>(), L->fwsxy.as<double2>(),
+                       L->fwsw.as<double>(), fa.dead};
+    uint64_t* tsw = r.ts_role(kRoleFiw, pl.nfw);
+    hipLaunchKernelGGL(fiw_kern(counts, mat, pl.mesh), dim3(pl.nfw), dim3(kFwThreads), 0, s, tsw, fa);
+    HCK(hipGetLastError());
+    if (ctx->host_stats) h3 = hclk::now();
+    FinBest fb = fin_best(r, pl.nfin2);
+    if (rq.d_best) {
+        fb.hint = L->fwhint.as<int>();   // (read and cleared by the argmin's last block)
+        fb.hint_host = L->d_dc + 8;
+        fb.nhint = kFwHints;
     }
-    uint64_t* tsf = ts_c >= 0 ? take_ts(nfin, ts_f, ts_nf) : nullptr;
+    uint64_t* tsf = r.ts_role(kRoleFin2, pl.nfin2);
+    // (fb.np: the pipelined loop's update of an xy-only poll, a generated source)
+    hipLaunchKernelGGL(fin2_kern(counts, mat, fb.np != 0, pl.mesh), dim3(pl.nfin2), dim3(kF2Threads), 0, s,
+                       counts ? L->frows.as<unsigned>() : nullptr, counts ? nullptr : L->frows.as<double>(),
+                       ldk, N, K, ctx->w0, r.d_vp, rq.d_area, rq.d_obj, fb, f2s, tsf);
+    HCK(hipGetLastError());
+    if (ctx->host_stats) {
+        const auto h4 = hclk::now();
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        ctx->hs_t[0] += std::chrono::duration<double>(h1 - t_poll_entry).count();
+        ctx->hs_t[1] += std::chrono::duration<double>(h2 - h1).count();
+        ctx->hs_t[2] += std::chrono::duration<double>(h3 - h2).count();
+        ctx->hs_t[3] += std::chrono::duration<double>(h4 - h3).count();
+        ++ctx->hs_n;
+    }
+    L->last_chain = 2;
+}
+
+// What the walks hand to finalize_kernel (k_final.h).
+struct WalkOut {
+    int n_other = 1;                   // partial rows per candidate of the scan / per-candidate walk
+    const int* d_umap = nullptr;       // poll walk: candidate -> distinct-disk position
+    const double* d_spart = nullptr;   // poll walk: shared-entry rows
+    const int* d_ncount = nullptr;
+};
+
+// The streaming scan: every entry against every candidate's disks.
+static void enqueue_scan(EvalRun& r, WalkOut& w)
+{
+    mac_ctx* ctx = r.ctx;
+    Lane* L = r.L;
+    const int N = r.rq.N, K = r.rq.K;
+    const int64_t M = ctx->M;
+    L->disks.reserve(sizeof(DiskRec) * (size_t)N * K);
+    hipLaunchKernelGGL(disk_prep_kernel, dim3(grid1d((int64_t)N * K, 256)), dim3(256), 0, r.s, r.rq.src, N, K,
+                       L->disks.as<DiskRec>());
+    HCK(hipGetLastError());
+    constexpr int KB = 4, PPT = 4;
+    const int64_t per_pass = (int64_t)kBlock * PPT;
+    int64_t nblk = std::max<int64_t>(1, (M + per_pass - 1) / per_pass);
+    const int kgroups = (K + KB - 1) / KB;
+    const int64_t want = std::max<int64_t>(1, (int64_t)(8 * ctx->cus) / kgroups);
+    nblk = std::min(nblk, want);
+    int64_t chunk = (M + nblk - 1) / nblk;
+    chunk = ((chunk + per_pass - 1) / per_pass) * per_pass;
+    nblk = std::max<int64_t>(1, (M + chunk - 1) / chunk);
+    w.n_other = (int)nblk;
+    L->partial.reserve(sizeof(double) * (size_t)K * nblk);
+    uint64_t* ts = r.ts_lone(nblk * kgroups);
+    hipLaunchKernelGGL((coverage_scan_kernel<KB, PPT>), dim3((unsigned)nblk, (unsigned)kgroups), dim3(kBlock), 0,
+                       r.s, ts, ctx->xys.as<double2>(), ctx->ws.as<double>(), M, L->disks.as<DiskRec>(), N, K, chunk,
+                       L->partial.as<double>());
+    HCK(hipGetLastError());
+}
+
+// The per-candidate walk alone (small batches, the single-candidate closure): the identity map, one
+// thread per (disk, candidate), no key pass.
+static void enqueue_small_walk(EvalRun& r, WalkOut& w)
+{
+    mac_ctx* ctx = r.ctx;
+    Lane* L = r.L;
+    const int N = r.rq.N, K = r.rq.K, G = r.pl.G;
+    L->disks.reserve(sizeof(DiskRec) * (size_t)N * K);
+    L->umap.reserve(sizeof(int) * (size_t)N * K);
+    L->ucount.reserve(sizeof(int) * (size_t)N);
+    w.n_other = G;
+    hipLaunchKernelGGL(disk_index_identity_kernel, dim3(grid1d((int64_t)N * K, 256)), dim3(256), 0, r.s, r.rq.src,
+                       N, K, L->disks.as<DiskRec>(), L->umap.as<int>());
+    HCK(hipGetLastError());
+    L->partial.reserve(sizeof(double) * (size_t)K * G);
+    uint64_t* ts = r.ts_lone(r.pl.units);
+    hipLaunchKernelGGL(coverage_tiled_kernel, dim3((unsigned)r.pl.units), dim3(kBlock), (uint32_t)tiled_lds_bytes(N),
+                       r.s, ts, ctx->xys.as<double2>(), ctx->ws.as<double>(), ctx->off.as<int32_t>(), ctx->grid,
+                       L->disks.as<DiskRec>(), L->umap.as<int>(), N, K, G, nullptr, L->partial.as<double>());
+    HCK(hipGetLastError());
+}
+
+// The prep launch of the five-launch chain, and of an evaluation without a chain that wants
+// objectives (the penalties alone). `keyed`: the source the index reads the keys through.
+static void enqueue_prep_five(EvalRun& r, CandSrc& keyed)
+{
+    const EvalPlan& pl = r.pl;
+    PrepArgs pr = prep_args(r, pl.nrec, keyed);
+    if (pl.poll_possible) {
+        r.L->prec.reserve(sizeof(int4) * (size_t)pl.nrec * r.rq.N);
+        pr.prec = r.L->prec.as<int4>();
+    }
+    uint64_t* tsk = pl.poll_possible ? r.ts_role(kRolePrep, pl.nrec) : nullptr;
+    hipLaunchKernelGGL(prep_kern(pl.prep_five, pl.mesh), dim3((unsigned)pl.nrec), prep_block(pl.prep_five), 0, r.s,
+                       tsk, pr);
+    HCK(hipGetLastError());
+}
+
+// The shared entries of crowded polls: the union pass (equal weights, k_or.h) or bit-words per
+// distinct position (k_bits.h); both return at once when few disks have neighbours (the poll
+// kernel took them).
+static void enqueue_shared_pass(EvalRun& r, int bits_on)
+{
+    mac_ctx* ctx = r.ctx;
+    Lane* L = r.L;
+    const int N = r.rq.N, K = r.rq.K;
+    const DiskRec* d_urec = L->disks.as<DiskRec>();
+    const int* d_map = L->umap.as<int>();
+    const unsigned nbits = (unsigned)std::max(1, std::min(N, ctx->cus));
+    const unsigned nor = (unsigned)(2 * ctx->cus);   // grid-strides over the listed jobs
+    uint64_t* tsg = r.ts_chain(kRoleShared, r.pl.counts ? nor : nbits);
+    if (r.pl.counts) {
+        OrArgs oa{};
+        oa.xy = ctx->xys.as<double2>();
+        oa.off = ctx->off.as<int32_t>();
+        oa.g = ctx->grid;
+        oa.urec = d_urec;
+        oa.umap = d_map;
+        oa.ucount = L->ucount.as<int>();
+        oa.region = L->region.as<int4>();
+        oa.nbrT = L->nbr.as<uint16_t>();
+        oa.nboxT = L->nboxT.as<int4>();
+        oa.ncount = L->ncount.as<int>();
+        oa.nboxU = L->nboxU.as<int4>();
+        oa.ncountU = L->ncountU.as<int>();
+        oa.lane4 = L->lane4.as<float4>();
+        oa.lanexp = L->lanexp.as<float>();
+        oa.jobs = L->orjobs.as<int2>();
+        oa.dcount = L->mode.as<int>() + 1;
+        oa.mode = r.d_mode;
+        oa.spart = L->spart.as<unsigned>();
+        oa.N = N;
+        oa.K = K;
+        oa.bits_on = bits_on;
+        oa.cap = (int)(ctx->M / kOrE + N + 64);
+        hipLaunchKernelGGL(shared_or_kernel, dim3(nor), dim3(kOrThreads), 0, r.s, tsg, oa);
+    } else
+        hipLaunchKernelGGL(shared_bits_kernel<false>, dim3(nbits), dim3(kBitsThreads), 0, r.s, tsg,
+                           ctx->xys.as<double2>(), ctx->ws.as<double>(), ctx->off.as<int32_t>(), ctx->grid, d_urec,
+                           d_map, L->ucount.as<int>(), L->region.as<int4>(), L->nbr.as<uint16_t>(),
+                           L->lane4.as<float4>(), L->lanexp.as<float>(), L->ncount.as<int>(), L->qual.as<int>(),
+                           L->mode.as<int>() + 1, r.d_mode, N, K, L->spart.as<double>(),
+                           bits_on == 2 ? 0 : kBitsMinDisks);
+    HCK(hipGetLastError());
+}
+
+// The shared-entry pass's launch hint (the walk set-up, the poll walk and the pass itself read it):
+// 0: fp64 jobs; 1: above kBitsMinDisks disks with neighbours; 2: always. Launched when one of the
+// lane's last 8 polls had more than kBitsMinDisks disks with neighbours (the poll kernel writes the
+// count to mapped host memory): a hint only, the poll kernel takes every disk when it is not
+// launched (MADS alternates crowded and quiet polls, and a crowded poll without the pass costs
+// several times its launch).
+static int shared_pass_hint(mac_ctx* ctx, Lane* L)
+{
+    const int dc_now = *(volatile int*)L->h_dc.p;   // 1 << 30 until a poll wrote it
+    int dc_max = dc_now;
+    if (dc_now < (1 << 30)) {
+        for (int q = 7; q > 0; --q) L->dc_hist[q] = L->dc_hist[q - 1];
+        L->dc_hist[0] = dc_now;
+        for (int q = 0; q < 8; ++q) dc_max = std::max(dc_max, L->dc_hist[q]);
+    }
+    int bits_on = ctx->shared_mode == MAC_SHARED_BITS ? 2
+                : ctx->shared_mode == MAC_SHARED_FP64 ? 0
+                : dc_max > kBitsMinDisks ? 1 : 0;
+    // Both passes stage an entry as its fp32 offset (u, v) from a region's centre with
+    // q = u u + v v, and q = +inf marks "no entry" (k_or.h, k_bits.h: outside the box, past
+    // the list, non-finite). A finite entry must therefore keep q finite: |u|, |v| below
+    // 2^63. Offsets are bounded by the grid's extent, so on a grid of 2^62 or more (a far
+    // outlier sets the pitch: the centre of the tile that holds the rest of the list lies
+    // S / 2 away from it) finite entries would drop out of the unions, and the poll
+    // kernel's fp64 jobs take every disk there.
+    const Grid& gr = ctx->grid;
+    if (!(((double)std::max(gr.nTx, gr.nTy) + 1.0) * gr.S < 0x1p62)) bits_on = 0;
+    return bits_on;
+}
+
+// The five-launch chain after its prep: the disk index (distinct disks per UAV, their records, the
+// map and the poll walk's lane constants, k_index.h), the walk set-up, the walks and the shared pass.
+// `keyed`: the source with the prep's key rows.
+static void enqueue_five(EvalRun& r, const CandSrc& keyed, WalkOut& w)
+{
+    const EvalReq& rq = r.rq;
+    const EvalPlan& pl = r.pl;
+    mac_ctx* ctx = r.ctx;
+    Lane* L = r.L;
+    hipStream_t s = r.s;
+    const int N = rq.N, K = rq.K, G = pl.G, counts = pl.counts;
+    L->disks.reserve(sizeof(DiskRec) * (size_t)N * K);
+    L->umap.reserve(sizeof(int) * (size_t)N * K);
+    L->ucount.reserve(sizeof(int) * (size_t)N);
+    // the poll walk's lane constants and row descriptors
+    L->lane4.reserve(sizeof(float4) * (size_t)N * K);
+    L->lanexp.reserve(sizeof(float) * (size_t)N * K);
+    L->rows.reserve(sizeof(int2) * (size_t)N * (kRowInfo + 1));
+    w.n_other = G;
+    const DiskRec* d_urec = L->disks.as<DiskRec>();
+    const int* d_map = L->umap.as<int>();
+    L->region.reserve(sizeof(int4) * N);
+    L->cost.reserve(sizeof(double2) * N);
+    L->mode.reserve((1 + kDcCount) * sizeof(int));  // [0] walk, [1..kDcCount] the poll walk's counters (k_common.h)
+    const IndexOut io{L->disks.as<DiskRec>(), L->umap.as<int>(), L->ucount.as<int>(),
+                      L->region.as<int4>(), L->cost.as<double2>(), L->mode.as<int>() + 1,
+                      L->prec.as<int4>(), pl.nrec,
+                      L->lane4.as<float4>(), L->lanexp.as<float>(), L->rows.as<int2>(),
+                      ctx->off.as<int32_t>(),
+                      // cons3 failures are not evaluated (objective +inf) unless the caller
+                      // also wants every candidate's area
+                      rq.d_area ? nullptr : r.d_vp};
+    uint64_t* tsi = r.ts_chain(kRoleIndex, pl.nidx);
+    hipLaunchKernelGGL(index_kern(keyed.keysT != nullptr, pl.iper == kIdxPerWide, keyed.np != 0, pl.mesh),
+                       dim3(pl.nidx), dim3(kIdxThreads), 0, s, tsi, keyed, N, K, ctx->grid, pl.iper ? 1 : 0, io);
+    HCK(hipGetLastError());
+    // launch hints from the lane's previous polls (mapped host memory the poll kernel
+    // writes): disks with neighbours, most positions of a disk, the walk AUTO would choose
+    ensure_hints(L);
+    // neighbour lists (k_walk.h walk_setup_kernel), then — when the per-candidate walk is
+    // forced, or AUTO chose it on one of the lane's last 8 polls — the walk choice and that
+    // walk (coverage_tiled_poll_kernel). Otherwise the poll walk runs; its kernel records
+    // the choice AUTO would have made, so a batch that favours the per-candidate walk gets
+    // it from the lane's next poll on (the choice only changes speed, never results).
+    // (a lane's first poll has no report yet: it launches the kernel once, and the
+    // sentinel stays out of the history)
+    const int walk_now = ((volatile int*)L->h_dc.p)[4];
+    bool hinted = walk_now == 0;
+    if (!hinted) {
+        for (int q = 7; q > 0; --q) L->walk_hist[q] = L->walk_hist[q - 1];
+        L->walk_hist[0] = walk_now;
+    }
+    for (int q = 0; q < 8; ++q) hinted |= L->walk_hist[q] == kModeTiled;
+    const bool run_tiled = pl.walk_forced == kModeTiled || (pl.walk_forced == 0 && hinted);
+    L->nbr.reserve(sizeof(uint16_t) * (size_t)N * kPollNbr);
+    L->ncount.reserve(sizeof(int) * (size_t)N);
+    L->dlist.reserve(sizeof(int) * (size_t)N);
+    L->qual.reserve(sizeof(int) * (size_t)N);
+    L->nboxT.reserve(sizeof(int4) * (size_t)N * kPollNbr);
+    L->partial.reserve(sizeof(double) * (size_t)K * std::max(G, N));
+    const int bits_on = shared_pass_hint(ctx, L);
+    // equal weights: the union pass (k_or.h), whose jobs walk_setup lists with the upper
+    // neighbour boxes; weighted lists: the bit-word kernel (k_bits.h)
+    OrSetup orj{};
+    if (bits_on && counts) {
+        L->nboxU.reserve(sizeof(int4) * (size_t)N * kPollNbr);
+        L->ncountU.reserve(sizeof(int) * (size_t)N);
+        const int64_t cap = ctx->M / kOrE + N + 64;   // the owned sets are disjoint
+        L->orjobs.reserve(sizeof(int2) * (size_t)cap * kOrBuckets);   // a list per bucket
+        orj = OrSetup{L->nboxU.as<int4>(), L->ncountU.as<int>(), L->orjobs.as<int2>(), (int)cap,
+                      ctx->off.as<int32_t>(), ctx->grid, L->ucount.as<int>()};
+    }
+    uint64_t* tss = r.ts_chain(kRoleSetup, N);
+    hipLaunchKernelGGL(walk_setup_kernel, dim3((unsigned)N), dim3(kBlock), 0, s, tss, N,
+                       L->region.as<int4>(), L->nbr.as<uint16_t>(), L->nboxT.as<int4>(),
+                       L->ncount.as<int>(), L->dlist.as<int>(), L->mode.as<int>() + 1,
+                       L->mode.as<int>(), L->qual.as<int>(), rq.src.mst, orj);
+    HCK(hipGetLastError());
+    if (run_tiled) {
+        // one workgroup per CU at most, grid-striding over the (candidate, slice) units
+        const unsigned nwg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(pl.units, ctx->cus));
+        uint64_t* ts = r.ts_role(kRoleTiledPoll, nwg);
+        hipLaunchKernelGGL(coverage_tiled_poll_kernel, dim3(nwg), dim3(kBlock),
+                           (uint32_t)tiled_lds_bytes(N), s, ts, ctx->xys.as<double2>(),
+                           ctx->ws.as<double>(), ctx->off.as<int32_t>(), ctx->grid, d_urec, d_map,
+                           N, K, G, L->mode.as<int>(), L->partial.as<double>(),
+                           L->nbr.as<uint16_t>(), L->ncount.as<int>(), L->cost.as<double2>(),
+                           kPollCostRatio, pl.walk_forced, L->d_dc + 4);
+        HCK(hipGetLastError());
+    }
+    r.d_mode = L->mode.as<int>();
+    w.d_umap = d_map;
+    // walk rows: the lane's last 8 polls' most distinct positions of a disk (poll kernel
+    // hint), one row per kPollKPB-position slice up to 4 (further slices loop)
+    const int um_now = ((volatile int*)L->h_dc.p)[2];
+    for (int q = 7; q > 0; --q) L->um_hist[q] = L->um_hist[q - 1];
+    L->um_hist[0] = um_now;
+    int um_max = 0;
+    for (int q = 0; q < 8; ++q) um_max = std::max(um_max, L->um_hist[q]);
+    const int gy = std::max(1, std::min(4, (um_max + kPollKPB - 1) / kPollKPB));
+    L->spart.reserve(sizeof(double) * (size_t)N * K);
+    const int n_shared = kSharedWG;
+    const dim3 pgrid(pl.nidx + n_shared, gy);   // walk workgroups (8 per disk group), then shared
+    uint64_t* ts = r.ts_role(kRolePoll, (int64_t)pgrid.x * pgrid.y);
+    hipLaunchKernelGGL(coverage_poll_kernel, pgrid, dim3(kPollThreads), 0, s, ts,
+                       ctx->xys.as<double2>(), ctx->ws.as<double>(),
+                       ctx->off.as<int32_t>(), ctx->grid, d_urec, d_map,
+                       L->ucount.as<int>(), L->region.as<int4>(), L->nbr.as<uint16_t>(),
+                       L->nboxT.as<int4>(), L->lane4.as<float4>(), L->lanexp.as<float>(),
+                       L->rows.as<int2>(),
+                       L->ncount.as<int>(), L->dlist.as<int>(), L->mode.as<int>() + 1,
+                       L->mode.as<int>() + 2, N, K,
+                       r.d_mode, L->partial.as<double>(), L->spart.as<double>(), n_shared, counts,
+                       bits_on, L->d_dc, L->qual.as<int>(),
+                       pl.walk_forced == 0 ? L->cost.as<double2>() : nullptr, kPollCostRatio);
+    HCK(hipGetLastError());
+    if (bits_on) enqueue_shared_pass(r, bits_on);
+    w.d_spart = L->spart.as<double>();
+    w.d_ncount = L->ncount.as<int>();
+}
+
+// finalize_kernel, with the poll argmin taken by its last-arriving block (k_final.h).
+static void enqueue_finalize(EvalRun& r, const WalkOut& w)
+{
+    const EvalReq& rq = r.rq;
+    const EvalPlan& pl = r.pl;
+    const FinBest fb = fin_best(r, pl.nfin);
+    uint64_t* tsf = r.ts_chain(kRoleFin, pl.nfin);
     // (fb.np: the pipelined loop's update of an xy-only poll)
     // (... and on a mesh: the builds with the scaled update; a stepper's finalize applies none)
-    const bool fm = mesh && fb.st != nullptr;
-    const auto fin_kern = fm ? (fb.np ? finalize_kernel<true, true> : finalize_kernel<false, true>)
-                             : fb.np ? finalize_kernel<true> : finalize_kernel<false>;
-    hipLaunchKernelGGL(fin_kern, dim3(nfin), dim3(kFinThreads), 0, s,
-                       L->partial.as<double>(), d_mode, n_poll, n_other, K, N, d_umap, d_spart, d_ncount,
-                       counts, ctx->w0, d_vp, d_area, d_obj, fb, tsf);
+    hipLaunchKernelGGL(finalize_kern(fb.np != 0, pl.mesh && fb.st != nullptr), dim3(pl.nfin), dim3(kFinThreads), 0,
+                       r.s, r.L->partial.as<double>(), r.d_mode, rq.N, w.n_other, rq.K, rq.N, w.d_umap, w.d_spart,
+                       w.d_ncount, pl.counts, r.ctx->w0, r.d_vp, rq.d_area, rq.d_obj, fb, tsf);
     HCK(hipGetLastError());
-    prof_end();
+}
+
+// What eval_plan reads of a request on this context (mask: a feasibility byte per candidate).
+static RouteIn route_in(const mac_ctx* ctx, const EvalReq& rq, bool mask)
+{
+    const CandSrc& src = rq.src;
+    RouteIn in;
+    in.algo = ctx->algo;
+    in.chain = ctx->chain;
+    in.cus = ctx->cus;
+    in.M = ctx->M;
+    in.w_uniform = ctx->w_uniform;
+    in.kind = src.cands ? RouteIn::kMatrix : src.ltri ? RouteIn::kBasis : RouteIn::kGenerated;
+    in.np = src.np;
+    in.k0 = src.k0;
+    in.mesh = src.mesh() != nullptr;
+    in.mst = src.mst != nullptr;
+    in.route_five = src.route_five != 0;
+    in.b = src.b;
+    in.delta = src.delta;
+    in.want_area = rq.d_area != nullptr;
+    in.want_obj = rq.d_obj != nullptr;
+    in.cons3 = rq.d_prev != nullptr;
+    in.mask = mask;
+    in.tiled = rq.tiled;
+    in.N = rq.N;
+    in.K = rq.K;
+    return in;
+}
+
+// Enqueue one evaluation on stream s: the route (eval_plan), a generated poll's mask launches, then
+// the fused chain, or the prep launch + index + walks + finalize (+ argmin).
+static void enqueue_eval(mac_ctx* ctx, Lane* L, hipStream_t s, const EvalReq& rq)
+{
+    const int K = rq.K;
+    const bool gen_masks = (rq.cons || rq.prog) && !rq.src.cands && rq.d_obj && K > 0;
+    const EvalPlan pl = eval_plan(route_in(ctx, rq, gen_masks));
+    EvalRun r{ctx, L, s, rq, pl};
+    if (rq.d_obj) {
+        L->vp.reserve(sizeof(double) * (size_t)std::max(K, 1));
+        r.d_vp = L->vp.as<double>();
+    }
+    if (gen_masks) enqueue_gen_masks(r);
+    // the history is read and updated at every eligible poll, also one whose chain is forced
+    if (pl.fused_eligible && (fused_history_allows(ctx, L) || ctx->chain == MAC_CHAIN_FUSED)) {
+        enqueue_fused(r);
+        r.prof_end();
+        return;
+    }
+    if (pl.poll_possible) L->last_chain = 1;
+    CandSrc keyed = rq.src;
+    if (pl.prep_five_runs) enqueue_prep_five(r, keyed);
+    WalkOut w;
+    if (rq.N == 0 || ctx->M == 0) {  // no UAV or no entry: every area is 0 (the loops never run)
+        L->partial.reserve(sizeof(double) * (size_t)K);
+        HCK(hipMemsetAsync(L->partial.p, 0, sizeof(double) * (size_t)K, s));
+    } else if (!rq.tiled)
+        enqueue_scan(r, w);
+    else if (!pl.poll_possible)
+        enqueue_small_walk(r, w);
+    else
+        enqueue_five(r, keyed, w);
+    enqueue_finalize(r, w);
+    r.prof_end();
 }
 
 static double dlim_threshold(double d) { return mac::dlim_threshold(d); }
+
+// cons3's inputs into the lane, on s: prev (3N) into L->prev, d_lim thresholded per UAV into L->dlim
+// (on the host: L->h_dlim) and as it is into L->dlimraw.
+template <class T>
+static void cons3_upload(Lane* L, hipStream_t s, int N, const T* prev, const double* d_lim)
+{
+    const int64_t three_n = 3 * (int64_t)N;
+    L->prev.reserve(sizeof(double) * three_n);
+    L->dlim.reserve(sizeof(double) * N);
+    L->dlimraw.reserve(sizeof(double) * N);
+    L->h_dlim.resize(N);
+    for (int i = 0; i < N; ++i) L->h_dlim[i] = dlim_threshold(d_lim[i]);
+    if constexpr (std::is_same<T, float>::value)
+        upload_widen(prev, three_n, L->p32, L->prev.as<double>(), s);
+    else
+        HCK(hipMemcpyAsync(L->prev.p, prev, sizeof(double) * three_n, hipMemcpyHostToDevice, s));
+    HCK(hipMemcpyAsync(L->dlim.p, L->h_dlim.data(), sizeof(double) * N, hipMemcpyHostToDevice, s));
+    HCK(hipMemcpyAsync(L->dlimraw.p, d_lim, sizeof(double) * N, hipMemcpyHostToDevice, s));
+}
 
 static int32_t check_common(mac_ctx* ctx, int64_t three_n, int64_t K)
 {
@@ -1462,22 +1450,14 @@ static void cons_mask_enqueue(hipStream_t s, const double* d_cands, int N, int64
 {
     constexpr int64_t kMaxWG = (int64_t)1 << 23;   // workgroups per launch (2^31 threads)
     const int S = cons_slots(N);                   // UAVs per thread: 1, 2, 4, 8 (N <= 2048)
-    void (*const kern)(const double*, int, ConsArgs, uint8_t*) =
-        S == 1 ? cons_mask_kernel<1> : S == 2 ? cons_mask_kernel<2> : S == 4 ? cons_mask_kernel<4> : cons_mask_kernel<8>;
-    // under a mac_motion: with d_sep off, the kernel without the sort and its LDS arrays
-    void (*const kmot)(const double*, int, ConsArgs, MotionArgs, uint8_t*) =
-        a.sep ? (S == 1 ? cons_mask_motion_kernel<1, true> : S == 2 ? cons_mask_motion_kernel<2, true>
-               : S == 4 ? cons_mask_motion_kernel<4, true> : cons_mask_motion_kernel<8, true>)
-              : (S == 1 ? cons_mask_motion_kernel<1, false> : S == 2 ? cons_mask_motion_kernel<2, false>
-               : S == 4 ? cons_mask_motion_kernel<4, false> : cons_mask_motion_kernel<8, false>);
-    const uint32_t lds = (mot && !a.sep) ? 0u : (uint32_t)(17 * kConsBlock * S);   // x, y, cell per sorted position
+    const uint32_t lds = (mot && !a.sep) ? 0u : mask_lds(S);
     for (int64_t k0 = 0; k0 < K; k0 += kMaxWG) {
         const int64_t B = std::min(kMaxWG, K - k0);
         if (mot)
-            hipLaunchKernelGGL(kmot, dim3((unsigned)B), dim3(kConsBlock), lds, s,
+            hipLaunchKernelGGL(mask_motion_kern(S, a.sep), dim3((unsigned)B), dim3(kConsBlock), lds, s,
                                d_cands + (size_t)k0 * (size_t)(3 * N), N, a, *mot, d_feas + k0);
         else
-            hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kConsBlock), lds, s,
+            hipLaunchKernelGGL(mask_kern(S), dim3((unsigned)B), dim3(kConsBlock), lds, s,
                                d_cands + (size_t)k0 * (size_t)(3 * N), N, a, d_feas + k0);
         HCK(hipGetLastError());
     }
@@ -1549,18 +1529,7 @@ static int32_t host_eval(mac_ctx* ctx, const T* cands, int64_t three_n, int64_t 
     double* d_dlimT = nullptr;
     if (want_obj && prev && N > 0) {
         if (!d_lim) return fail(MAC_E_INVAL, "prev given without d_lim");
-        L->prev.reserve(sizeof(double) * three_n);
-        L->dlim.reserve(sizeof(double) * N);
-        L->dlimraw.reserve(sizeof(double) * N);
-        L->h_dlim.resize(N);
-        for (int i = 0; i < N; ++i) L->h_dlim[i] = dlim_threshold(d_lim[i]);
-        if constexpr (f32)
-            upload_widen(prev, three_n, L->p32, L->prev.as<double>(), s);
-        else
-            HCK(hipMemcpyAsync(L->prev.p, prev, sizeof(double) * three_n, hipMemcpyHostToDevice, s));
-        HCK(hipMemcpyAsync(L->dlim.p, L->h_dlim.data(), sizeof(double) * N, hipMemcpyHostToDevice,
-                           s));
-        HCK(hipMemcpyAsync(L->dlimraw.p, d_lim, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        cons3_upload(L, s, N, prev, d_lim);
         d_prev = L->prev.as<double>();
         d_dlimT = L->dlim.as<double>();
     }
@@ -1581,11 +1550,21 @@ static int32_t host_eval(mac_ctx* ctx, const T* cands, int64_t three_n, int64_t 
         if (motion) mot = motion_upload(L, s, N, motion);   // (mac_poll_best_motion_f64: a constraint is on)
         cons_mask_enqueue(s, L->cands.as<double>(), N, K, *cons, L->cmask.as<uint8_t>(), motion ? &mot : nullptr);
     }
-    enqueue_eval(ctx, L, s, matrix_src(L->cands.as<double>(), N), N, (int)K, tiled, d_rmax, penalty, d_prev,
-                 d_dlimT, d_prev ? L->dlimraw.as<double>() : nullptr, tan_half_fov,
-                 area_out ? L->area.as<double>() : nullptr,
-                 want_obj ? L->obj.as<double>() : nullptr,
-                 (best_obj || best_idx) ? L->best.as<double>() : nullptr, 0);
+    EvalReq rq;
+    rq.src = matrix_src(L->cands.as<double>(), N);
+    rq.N = N;
+    rq.K = (int)K;
+    rq.tiled = tiled;
+    rq.d_rmax = d_rmax;
+    rq.penalty = penalty;
+    rq.d_prev = d_prev;
+    rq.d_dlimT = d_dlimT;
+    rq.d_dlim_raw = d_prev ? L->dlimraw.as<double>() : nullptr;
+    rq.tan_half_fov = tan_half_fov;
+    rq.d_area = area_out ? L->area.as<double>() : nullptr;
+    rq.d_obj = want_obj ? L->obj.as<double>() : nullptr;
+    rq.d_best = (best_obj || best_idx) ? L->best.as<double>() : nullptr;
+    enqueue_eval(ctx, L, s, rq);
     if (cons)
         cons_argmin_enqueue(s, L->obj.as<double>(), L->cmask.as<uint8_t>(), K, 0, L->best.p, nullptr, 0);
     // results: into the pinned buffer (the upload has completed before the kernels ran), then
@@ -1658,19 +1637,13 @@ static int32_t host_eval_basis(mac_ctx* ctx, const double* x_inc, int64_t three_
     double* d_prev = nullptr;
     double* d_dlimT = nullptr;
     if (prev) {
-        L->prev.reserve(sizeof(double) * three_n);
-        L->dlim.reserve(sizeof(double) * N);
-        L->dlimraw.reserve(sizeof(double) * N);
-        L->h_dlim.resize(N);
-        for (int i = 0; i < N; ++i) L->h_dlim[i] = dlim_threshold(d_lim[i]);
-        HCK(hipMemcpyAsync(L->prev.p, prev, sizeof(double) * three_n, hipMemcpyHostToDevice, s));
-        HCK(hipMemcpyAsync(L->dlim.p, L->h_dlim.data(), sizeof(double) * N, hipMemcpyHostToDevice, s));
-        HCK(hipMemcpyAsync(L->dlimraw.p, d_lim, sizeof(double) * N, hipMemcpyHostToDevice, s));
+        cons3_upload(L, s, N, prev, d_lim);
         d_prev = L->prev.as<double>();
         d_dlimT = L->dlim.as<double>();
     }
     unsigned char* d = (unsigned char*)L->cands.p;
-    CandSrc src{};
+    EvalReq rq;
+    CandSrc& src = rq.src;
     src.xinc = (const double*)d;
     src.rp = (const int*)(d + 8 * n);
     src.cp = (const int*)(d + 12 * n);
@@ -1679,9 +1652,18 @@ static int32_t host_eval_basis(mac_ctx* ctx, const double* x_inc, int64_t three_
     src.b = bmax;
     src.k0 = 0;
     src.route_five = host_crowded_disks(x_inc, N, (double)bmax * std::fabs(delta), ctx->grid.S) > kBitsMinDisks;
-    enqueue_eval(ctx, L, s, src, N, (int)K, use_tiled(ctx, N, nullptr, three_n), L->rmax.as<double>(),
-                 penalty, d_prev, d_dlimT, d_prev ? L->dlimraw.as<double>() : nullptr, tan_half_fov,
-                 nullptr, L->obj.as<double>(), L->best.as<double>(), 0);
+    rq.N = N;
+    rq.K = (int)K;
+    rq.tiled = use_tiled(ctx, N, nullptr, three_n);
+    rq.d_rmax = L->rmax.as<double>();
+    rq.penalty = penalty;
+    rq.d_prev = d_prev;
+    rq.d_dlimT = d_dlimT;
+    rq.d_dlim_raw = d_prev ? L->dlimraw.as<double>() : nullptr;
+    rq.tan_half_fov = tan_half_fov;
+    rq.d_obj = L->obj.as<double>();
+    rq.d_best = L->best.as<double>();
+    enqueue_eval(ctx, L, s, rq);
     // (the upload completed before the kernels ran: the staging takes the results)
     double* ho = (double*)L->h_io.p;
     double* hb = ho + (obj_out ? K : 0);
@@ -1815,6 +1797,57 @@ int32_t mac_diag_tiles(double c, double r, double g0, double invS, int32_t n, in
     out[1] = tile_span(c, r, g0, invS, n, lo, hi) ? 1 : 0;
     out[2] = lo;
     out[3] = hi;
+    return MAC_OK;
+}
+
+// host only, every build (not declared in maxcover.h): the route enqueue_eval plans (eval_plan.h)
+// for in = {algo, chain, cus, M, w_uniform, kind (RouteIn::Kind), np, k0, mesh, mst, route_five, b,
+// want_area, want_obj, cons3, mask, tiled, N, K} and the basis form's delta; the first n_out of
+// out = {poll_possible, walk_forced, iper, want_keys, pair, gen_x, mesh, nchain, G, units,
+// fused_eligible, excl, counts, prep_fused (PrepKind), nprep, xbase, prep_five_runs, prep_five, nrec,
+// nfw, nidx, nfin2, nfin}
+int32_t mac_diag_route(const int64_t* in, double delta, int64_t* out, int32_t n_out)
+{
+    if (!in || !out || n_out < 0 || in[17] < 0 || in[18] < 1) return MAC_E_INVAL;
+    RouteIn ri;
+    ri.algo = (int)in[0];
+    ri.chain = (int)in[1];
+    ri.cus = (int)in[2];
+    ri.M = in[3];
+    ri.w_uniform = in[4] != 0;
+    ri.kind = (int)in[5];
+    ri.np = (int)in[6];
+    ri.k0 = (int)in[7];
+    ri.mesh = in[8] != 0;
+    ri.mst = in[9] != 0;
+    ri.route_five = in[10] != 0;
+    ri.b = in[11];
+    ri.delta = delta;
+    ri.want_area = in[12] != 0;
+    ri.want_obj = in[13] != 0;
+    ri.cons3 = in[14] != 0;
+    ri.mask = in[15] != 0;
+    ri.tiled = in[16] != 0;
+    ri.N = (int)in[17];
+    ri.K = (int)in[18];
+    const EvalPlan p = eval_plan(ri);
+    const int64_t v[] = {p.poll_possible, p.walk_forced, p.iper, p.want_keys, p.pair, p.gen_x, p.mesh, p.nchain,
+                         p.G, p.units, p.fused_eligible, p.excl, p.counts, p.prep_fused, p.nprep, p.xbase,
+                         p.prep_five_runs, p.prep_five, p.nrec, p.nfw, p.nidx, p.nfin2, p.nfin};
+    for (int q = 0; q < n_out && q < (int)(sizeof v / sizeof v[0]); ++q) out[q] = v[q];
+    return MAC_OK;
+}
+
+// host only, every build (not declared in maxcover.h): the workgroups that took stamps under each
+// launch role (mac_profile_kernels' roles) in the launches recorded since the last reset, summed
+int32_t mac_diag_role_slots(mac_ctx* ctx, int64_t* out, int32_t n_roles)
+{
+    if (!ctx || !out || n_roles < 0) return MAC_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    for (int r = 0; r < n_roles; ++r) out[r] = 0;
+    for (auto& p : ctx->prof)
+        for (int r = 0; r < n_roles && r < MAC_PROF_ROLES; ++r)
+            if (p.role[r][0] >= 0) out[r] += p.role[r][1];
     return MAC_OK;
 }
 
@@ -2757,17 +2790,40 @@ static void mads_make_slot(mac_mads* m)
     m->d_slot = (uint64_t*)dp;
 }
 
+// A stepper's poll of Kc candidates from src as a request: its penalty and cons3 inputs, the lane's
+// objectives, the poll's best, and the swarm and motion constraints that are on.
+static EvalReq mads_request(mac_mads* m, const CandSrc& src, int Kc)
+{
+    EvalReq rq;
+    rq.src = src;
+    rq.N = m->N;
+    rq.K = Kc;
+    rq.tiled = use_tiled(m->ctx, m->N, nullptr, m->n);
+    rq.d_rmax = m->L->rmax.as<double>();
+    rq.penalty = m->penalty;
+    rq.d_prev = m->d_prev;
+    rq.d_dlimT = m->d_dlimT;
+    rq.d_dlim_raw = m->d_prev ? m->L->dlimraw.as<double>() : nullptr;
+    rq.tan_half_fov = m->tan_half_fov;
+    rq.d_obj = m->L->obj.as<double>();
+    rq.d_best = mads_best_ptr(m);
+    rq.cons = m->has_cons ? &m->cons : nullptr;
+    rq.motion = m->has_mot ? &m->mot : nullptr;
+    return rq;
+}
+
 static void mads_best_of(mac_mads* m, const CandSrc& src, int Kc, int64_t idx_base, bool slot = false)
 {
     if (slot) mads_make_slot(m);
     m->slotted = slot;
-    enqueue_eval(m->ctx, m->L, m->s, src, m->N, Kc, use_tiled(m->ctx, m->N, nullptr, m->n),
-                 m->L->rmax.as<double>(), m->penalty, m->d_prev, m->d_dlimT,
-                 m->d_prev ? m->L->dlimraw.as<double>() : nullptr, m->tan_half_fov,
-                 nullptr, m->L->obj.as<double>(), mads_best_ptr(m), idx_base,
-                 slot ? m->d_slot : nullptr, slot ? ++m->seq : 0, nullptr,
-                 slot ? m->d_feas.as<unsigned long long>() : nullptr, m->has_cons ? &m->cons : nullptr,
-                 m->has_mot ? &m->mot : nullptr);
+    EvalReq rq = mads_request(m, src, Kc);
+    rq.idx_base = idx_base;
+    if (slot) {
+        rq.d_mirror = m->d_slot;
+        rq.mirror_seq = ++m->seq;
+        rq.d_feas = m->d_feas.as<unsigned long long>();
+    }
+    enqueue_eval(m->ctx, m->L, m->s, rq);
     if (!slot) HCK(hipMemcpyAsync(m->hb, mads_best_ptr(m), 16, hipMemcpyDeviceToHost, m->s));
 }
 
@@ -2806,17 +2862,8 @@ static void mads_free(mac_mads* m)
     delete m;
 }
 
-int32_t mac_mads_begin(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                       double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                       const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                       mac_mads** out)
-{
-    return mac_mads_begin_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
-                               shard_hi, out, nullptr);
-}
-
-// The opts of mac_mads_run_opts / mac_mads_begin_opts: MAC_E_INVAL on an unknown poll kind or a
-// non-zero reserved word; *xy = the xy-only poll (null opts: the full poll).
+// The opts of a run or a stepper: MAC_E_INVAL on an unknown poll kind or a non-zero reserved word;
+// *xy = the xy-only poll (null opts: the full poll).
 static int32_t mads_opts_check(const mac_mads_opts* opts, bool* xy)
 {
     *xy = false;
@@ -2829,52 +2876,63 @@ static int32_t mads_opts_check(const mac_mads_opts* opts, bool* xy)
     return MAC_OK;
 }
 
+// The mesh of a run or a stepper: MAC_E_INVAL on a non-zero reserved word or an entry that is not
+// finite and > 0, before the context is touched; *gran = the 3N host doubles, or null when the mesh
+// is the unit one (no mesh, no vector, or every entry exactly 1.0).
+static int32_t mads_mesh_check(const mac_mads_mesh* mesh, int64_t three_n, const double** gran)
+{
+    *gran = nullptr;
+    if (!mesh) return MAC_OK;
+    if (mesh->reserved != 0) return fail(MAC_E_INVAL, "mac_mads_mesh: reserved must be 0");
+    if (!mesh->granularity) return MAC_OK;
+    bool unit = true;
+    for (int64_t v = 0; v < three_n; ++v) {
+        const double g = mesh->granularity[v];
+        if (!(g > 0.0) || !std::isfinite(g))
+            return fail(MAC_E_INVAL, "mac_mads_mesh: granularity[" + std::to_string(v) +
+                                         "] is not finite and > 0");
+        unit = unit && g == 1.0;
+    }
+    if (!unit) *gran = mesh->granularity;
+    return MAC_OK;
+}
+
+// What the widest entry points (mac_mads_run_mesh / mac_mads_begin_mesh) take beyond the plain run;
+// the narrower ones leave the rest null. mads_setup_check fills xy and gran: the mesh's errors win
+// over the opts', and both over every check of the run itself.
+struct MadsSetup {
+    const mac_cons* cons = nullptr;
+    const mac_mads_opts* opts = nullptr;
+    const mac_motion* motion = nullptr;   // (every constraint off: as none)
+    const mac_mads_mesh* mesh = nullptr;
+    bool checked = false, xy = false;
+    const double* gran = nullptr;
+};
+
+static int32_t mads_setup_check(MadsSetup& su, int64_t three_n)
+{
+    if (su.checked) return MAC_OK;
+    int32_t rc = mads_mesh_check(su.mesh, three_n, &su.gran);
+    if (!rc) rc = mads_opts_check(su.opts, &su.xy);
+    su.checked = !rc;
+    return rc;
+}
+
 static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                                double penalty, const double* prev, const double* d_lim, double tan_half_fov,
                                const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                               mac_mads** out, const mac_cons* cons, bool xy,
-                               const mac_motion* motion = nullptr, const double* gran = nullptr);
-
-int32_t mac_mads_begin_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                            mac_mads** out, const mac_cons* cons)
-{
-    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
-                           shard_hi, out, cons, false);
-}
-
-int32_t mac_mads_begin_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                            mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts)
+                               mac_mads** out, MadsSetup su)
 {
     ABI_BEGIN
     if (!out) return fail(MAC_E_INVAL, "null out");
     *out = nullptr;
-    bool xy = false;
-    const int32_t rc = mads_opts_check(opts, &xy);
+    int32_t rc = mads_setup_check(su, three_n);
     if (rc) return rc;
-    if (!xy)   // the full poll: the calls as they are
-        return cons ? mac_mads_begin_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
-                                          shard_lo, shard_hi, out, cons)
-                    : mac_mads_begin(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
-                                     shard_lo, shard_hi, out);
-    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
-                           shard_hi, out, cons, true);
-    ABI_END
-}
-
-static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                               double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                               const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi,
-                               mac_mads** out, const mac_cons* cons, bool xy, const mac_motion* motion,
-                               const double* gran)
-{
-    ABI_BEGIN
-    if (!out) return fail(MAC_E_INVAL, "null out");
-    *out = nullptr;
-    int32_t rc = check_common(ctx, three_n, 1);
+    const mac_cons* cons = su.cons;
+    const mac_motion* motion = su.motion;
+    const double* gran = su.gran;
+    const bool xy = su.xy;
+    rc = check_common(ctx, three_n, 1);
     if (rc) return rc;
     if (!x0 || !r_max || !prm) return fail(MAC_E_INVAL, "null argument");
     if (prev && !d_lim) return fail(MAC_E_INVAL, "prev given without d_lim");
@@ -2931,20 +2989,12 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
         }
         if (prev) {
             m->h_prev.assign(prev, prev + three_n);
-            L->prev.reserve(sizeof(double) * three_n);
-            L->dlim.reserve(sizeof(double) * N);
-            L->dlimraw.reserve(sizeof(double) * N);
-            L->h_dlim.resize(N);
-            for (int i = 0; i < N; ++i) L->h_dlim[i] = dlim_threshold(d_lim[i]);
-            HCK(hipMemcpyAsync(L->prev.p, prev, sizeof(double) * three_n, hipMemcpyHostToDevice, s));
-            HCK(hipMemcpyAsync(L->dlim.p, L->h_dlim.data(), sizeof(double) * N,
-                               hipMemcpyHostToDevice, s));
-            HCK(hipMemcpyAsync(L->dlimraw.p, d_lim, sizeof(double) * N, hipMemcpyHostToDevice, s));
+            cons3_upload(L, s, N, prev, d_lim);
             m->d_prev = L->prev.as<double>();
             m->d_dlimT = L->dlim.as<double>();
         }
         m->x.assign(x0, x0 + three_n);
-        if (gran) {   // the mesh: validated by the caller (mads_mesh_check), copied here
+        if (gran) {   // the mesh: validated above (mads_setup_check), copied here
             m->g.assign(gran, gran + three_n);
             m->d_gran.reserve(sizeof(double) * three_n);
             // (pageable memory: the copy has left m->g when the call returns)
@@ -3277,7 +3327,7 @@ static constexpr uint64_t kMadsDoneSeq = 1ull << 62;   // seq word of a stopped 
 static bool mads_pipelinable(const mac_mads* m)
 {
     return m->lo == 0 && m->hi == m->K && !m->ext_best && m->prm.n_iter > 0 &&
-           poll_walk_possible(m->ctx, m->N, m->K, use_tiled(m->ctx, m->N, nullptr, m->n));
+           poll_walk_possible(m->ctx->algo, m->ctx->M, m->N, m->K, use_tiled(m->ctx, m->N, nullptr, m->n));
 }
 
 static void mads_run_pipelined(mac_mads* m)
@@ -3366,11 +3416,12 @@ static void mads_run_pipelined(mac_mads* m)
         fbm.np = src.np;
         fbm.ell_max = (int)m->prm.ell_max;
         fbm.done_seq = kMadsDoneSeq;
-        enqueue_eval(m->ctx, m->L, s, src, m->N, m->K, true, m->L->rmax.as<double>(), m->penalty,
-                     m->d_prev, m->d_dlimT, m->d_prev ? m->L->dlimraw.as<double>() : nullptr,
-                     m->tan_half_fov, nullptr, m->L->obj.as<double>(),
-                     m->L->best.as<double>(), 0, m->d_slot, (uint64_t)t, &fbm, &dst->feas,
-                     m->has_cons ? &m->cons : nullptr, m->has_mot ? &m->mot : nullptr);
+        EvalReq rq = mads_request(m, src, m->K);   // (pipelinable: the tiled family, the lane's best)
+        rq.d_mirror = m->d_slot;
+        rq.mirror_seq = (uint64_t)t;
+        rq.fb_mads = &fbm;
+        rq.d_feas = &dst->feas;
+        enqueue_eval(m->ctx, m->L, s, rq);
         const auto t3 = clk::now();
         if (computed < n_iter) {   // one iteration's permutations per poll, uploaded per chunk
             perms_of(++computed);
@@ -3400,57 +3451,18 @@ static void mads_run_pipelined(mac_mads* m)
     m->h_wait += std::chrono::duration<double>(clk::now() - t5).count();
 }
 
-int32_t mac_mads_run(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                     double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                     const mac_mads_params* prm, double* x_out, mac_mads_stats* st)
-{
-    return mac_mads_run_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
-                             nullptr);
-}
-
 static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                             const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                             bool xy, const mac_motion* motion = nullptr, const double* gran = nullptr);
-
-int32_t mac_mads_run_cons(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons)
-{
-    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons,
-                         false);
-}
-
-int32_t mac_mads_run_opts(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                          const mac_mads_opts* opts)
+                             const mac_mads_params* prm, double* x_out, mac_mads_stats* st, MadsSetup su)
 {
     ABI_BEGIN
-    bool xy = false;
-    const int32_t rc = mads_opts_check(opts, &xy);
+    int32_t rc = mads_setup_check(su, three_n);
     if (rc) return rc;
-    if (!xy)   // the full poll: the calls as they are
-        return cons ? mac_mads_run_cons(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm,
-                                        x_out, st, cons)
-                    : mac_mads_run(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out,
-                                   st);
-    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons,
-                         true);
-    ABI_END
-}
-
-static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                             double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                             const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                             bool xy, const mac_motion* motion, const double* gran)
-{
-    ABI_BEGIN
     if (!x_out) return fail(MAC_E_INVAL, "null argument");
     mac_mads* m = nullptr;
     // the whole poll: every candidate of the 2 n_p (n_p = 3N, or 2N for the xy-only poll)
-    int32_t rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
-                                 xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy, motion, gran);
+    rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
+                         su.xy ? 4 * (three_n / 3) : 2 * three_n, &m, su);
     if (rc) return rc;
     if (mads_pipelinable(m)) {
         try {
@@ -3476,6 +3488,57 @@ static int32_t mads_run_impl(mac_ctx* ctx, const double* x0, int64_t three_n, co
     return rc;
     ABI_END
 }
+
+// The entry points, narrowest first: each is the widest with what it lacks left null.
+#define MADS_RUN_ARGS                                                                                      \
+    mac_ctx *ctx, const double *x0, int64_t three_n, const double *r_max, double penalty, const double *prev, \
+        const double *d_lim, double tan_half_fov, const mac_mads_params *prm, double *x_out, mac_mads_stats *st
+#define MADS_RUN_PASS ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st
+#define MADS_BEGIN_ARGS                                                                                    \
+    mac_ctx *ctx, const double *x0, int64_t three_n, const double *r_max, double penalty, const double *prev, \
+        const double *d_lim, double tan_half_fov, const mac_mads_params *prm, int64_t shard_lo,            \
+        int64_t shard_hi, mac_mads **out
+#define MADS_BEGIN_PASS ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi, out
+
+int32_t mac_mads_run(MADS_RUN_ARGS) { return mads_run_impl(MADS_RUN_PASS, MadsSetup{}); }
+int32_t mac_mads_run_cons(MADS_RUN_ARGS, const mac_cons* cons) { return mads_run_impl(MADS_RUN_PASS, MadsSetup{cons}); }
+int32_t mac_mads_run_opts(MADS_RUN_ARGS, const mac_cons* cons, const mac_mads_opts* opts)
+{
+    return mads_run_impl(MADS_RUN_PASS, MadsSetup{cons, opts});
+}
+int32_t mac_mads_run_motion(MADS_RUN_ARGS, const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion)
+{
+    return mads_run_impl(MADS_RUN_PASS, MadsSetup{cons, opts, motion});
+}
+int32_t mac_mads_run_mesh(MADS_RUN_ARGS, const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
+                          const mac_mads_mesh* mesh)
+{
+    return mads_run_impl(MADS_RUN_PASS, MadsSetup{cons, opts, motion, mesh});
+}
+
+int32_t mac_mads_begin(MADS_BEGIN_ARGS) { return mads_begin_impl(MADS_BEGIN_PASS, MadsSetup{}); }
+int32_t mac_mads_begin_cons(MADS_BEGIN_ARGS, const mac_cons* cons)
+{
+    return mads_begin_impl(MADS_BEGIN_PASS, MadsSetup{cons});
+}
+int32_t mac_mads_begin_opts(MADS_BEGIN_ARGS, const mac_cons* cons, const mac_mads_opts* opts)
+{
+    return mads_begin_impl(MADS_BEGIN_PASS, MadsSetup{cons, opts});
+}
+int32_t mac_mads_begin_motion(MADS_BEGIN_ARGS, const mac_cons* cons, const mac_mads_opts* opts,
+                              const mac_motion* motion)
+{
+    return mads_begin_impl(MADS_BEGIN_PASS, MadsSetup{cons, opts, motion});
+}
+int32_t mac_mads_begin_mesh(MADS_BEGIN_ARGS, const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
+                            const mac_mads_mesh* mesh)
+{
+    return mads_begin_impl(MADS_BEGIN_PASS, MadsSetup{cons, opts, motion, mesh});
+}
+#undef MADS_RUN_ARGS
+#undef MADS_RUN_PASS
+#undef MADS_BEGIN_ARGS
+#undef MADS_BEGIN_PASS
 
 // The single-candidate closure (k_closure.h): the candidates written by the host straight into the
 // lane's fine-grained device buffer through the BAR (a large-BAR device; else pinned staging and a
@@ -3972,8 +4035,14 @@ int32_t mac_area_batch_dev_f64(mac_ctx* ctx, const double* d_cands, int64_t thre
     hipStream_t s = (hipStream_t)stream;   // NULL: HIP's null stream
     LaneGuard lg(ctx, s);
     const int N = (int)(three_n / 3);
-    enqueue_eval(ctx, lg.lane, s, matrix_src(d_cands, N), N, (int)K, use_tiled(ctx, N, nullptr, three_n), nullptr,
-                 0.0, nullptr, nullptr, nullptr, 1.0, d_area, nullptr, nullptr, 0);
+    EvalReq rq;
+    rq.src = matrix_src(d_cands, N);
+    rq.N = N;
+    rq.K = (int)K;
+    rq.tiled = use_tiled(ctx, N, nullptr, three_n);
+    rq.tan_half_fov = 1.0;
+    rq.d_area = d_area;
+    enqueue_eval(ctx, lg.lane, s, rq);
     return MAC_OK;
     ABI_END
 }
@@ -4223,20 +4292,34 @@ static int32_t poll_best_dev(mac_ctx* ctx, const T* d_cands_in, int64_t three_n,
     }
     uint64_t seq = 0;
     uint64_t* d_mirror = assign_mirror(ctx, d_best, &seq);
+    EvalReq rq;
+    rq.src = matrix_src(d_cands, N);
+    rq.N = N;
+    rq.K = (int)K;
+    rq.tiled = use_tiled(ctx, N, nullptr, three_n);
+    rq.d_rmax = d_rmax;
+    rq.penalty = penalty;
+    rq.d_prev = d_prev;
+    rq.d_dlimT = d_dlimT;
+    rq.d_dlim_raw = d_dlim;
+    rq.tan_half_fov = tan_half_fov;
+    rq.d_obj = d_o;
     if (cons) {
         // the masked poll (mac_poll_best_cons_dev_f64): the mask, the chain unchanged into the lane's
         // own best (no slot), then the masked argmin into d_o (in place), d_best and its slot
         L->cmask.reserve((size_t)K);
         L->cbest.reserve(16);
         cons_mask_enqueue(s, d_cands, N, K, *cons, L->cmask.as<uint8_t>());
-        enqueue_eval(ctx, L, s, matrix_src(d_cands, N), N, (int)K, use_tiled(ctx, N, nullptr, three_n), d_rmax,
-                     penalty, d_prev, d_dlimT, d_dlim, tan_half_fov, nullptr, d_o, L->cbest.as<double>(), 0);
+        rq.d_best = L->cbest.as<double>();
+        enqueue_eval(ctx, L, s, rq);
         cons_argmin_enqueue(s, d_o, L->cmask.as<uint8_t>(), K, idx_base, d_best, d_mirror, seq);
         return MAC_OK;
     }
-    enqueue_eval(ctx, L, s, matrix_src(d_cands, N), N, (int)K, use_tiled(ctx, N, nullptr, three_n), d_rmax,
-                 penalty, d_prev, d_dlimT, d_dlim, tan_half_fov, nullptr, d_o, (double*)d_best, idx_base,
-                 d_mirror, seq);
+    rq.d_best = (double*)d_best;
+    rq.idx_base = idx_base;
+    rq.d_mirror = d_mirror;
+    rq.mirror_seq = seq;
+    enqueue_eval(ctx, L, s, rq);
     return MAC_OK;
 }
 
@@ -4559,108 +4642,6 @@ int32_t mac_poll_best_motion_f64(mac_ctx* ctx, const double* cands, int64_t thre
     ABI_END
 }
 
-int32_t mac_mads_run_motion(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                            const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                            const mac_mads_opts* opts, const mac_motion* motion)
-{
-    bool mc, ms, ma;
-    if (!motion_on(motion, &mc, &ms, &ma))   // nothing on: the _opts call, untouched
-        return mac_mads_run_opts(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
-                                 cons, opts);
-    ABI_BEGIN
-    bool xy = false;
-    const int32_t rc = mads_opts_check(opts, &xy);
-    if (rc) return rc;
-    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons, xy,
-                         motion);
-    ABI_END
-}
-
-int32_t mac_mads_begin_motion(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                              double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                              const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi, mac_mads** out,
-                              const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion)
-{
-    bool mc, ms, ma;
-    if (!motion_on(motion, &mc, &ms, &ma))   // nothing on: the _opts call, untouched
-        return mac_mads_begin_opts(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
-                                   shard_hi, out, cons, opts);
-    ABI_BEGIN
-    if (!out) return fail(MAC_E_INVAL, "null out");
-    *out = nullptr;
-    bool xy = false;
-    const int32_t rc = mads_opts_check(opts, &xy);
-    if (rc) return rc;
-    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
-                           out, cons, xy, motion);
-    ABI_END
-}
-
-// The mesh of mac_mads_run_mesh / mac_mads_begin_mesh: MAC_E_INVAL on a non-zero reserved word or an
-// entry that is not finite and > 0, before the context is touched; *gran = the 3N host doubles, or
-// null when the mesh is the unit one (no mesh, no vector, or every entry exactly 1.0: the _motion call).
-static int32_t mads_mesh_check(const mac_mads_mesh* mesh, int64_t three_n, const double** gran)
-{
-    *gran = nullptr;
-    if (!mesh) return MAC_OK;
-    if (mesh->reserved != 0) return fail(MAC_E_INVAL, "mac_mads_mesh: reserved must be 0");
-    if (!mesh->granularity) return MAC_OK;
-    bool unit = true;
-    for (int64_t v = 0; v < three_n; ++v) {
-        const double g = mesh->granularity[v];
-        if (!(g > 0.0) || !std::isfinite(g))
-            return fail(MAC_E_INVAL, "mac_mads_mesh: granularity[" + std::to_string(v) +
-                                         "] is not finite and > 0");
-        unit = unit && g == 1.0;
-    }
-    if (!unit) *gran = mesh->granularity;
-    return MAC_OK;
-}
-
-int32_t mac_mads_run_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                          double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                          const mac_mads_params* prm, double* x_out, mac_mads_stats* st, const mac_cons* cons,
-                          const mac_mads_opts* opts, const mac_motion* motion, const mac_mads_mesh* mesh)
-{
-    ABI_BEGIN
-    const double* gran = nullptr;
-    int32_t rc = mads_mesh_check(mesh, three_n, &gran);
-    if (rc) return rc;
-    if (!gran)   // the unit mesh: the _motion call, untouched
-        return mac_mads_run_motion(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
-                                   cons, opts, motion);
-    bool xy = false;
-    rc = mads_opts_check(opts, &xy);
-    if (rc) return rc;
-    return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, cons, xy,
-                         motion, gran);
-    ABI_END
-}
-
-int32_t mac_mads_begin_mesh(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
-                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
-                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi, mac_mads** out,
-                            const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
-                            const mac_mads_mesh* mesh)
-{
-    ABI_BEGIN
-    if (!out) return fail(MAC_E_INVAL, "null out");
-    *out = nullptr;
-    const double* gran = nullptr;
-    int32_t rc = mads_mesh_check(mesh, three_n, &gran);
-    if (rc) return rc;
-    if (!gran)   // the unit mesh: the _motion call, untouched
-        return mac_mads_begin_motion(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo,
-                                     shard_hi, out, cons, opts, motion);
-    bool xy = false;
-    rc = mads_opts_check(opts, &xy);
-    if (rc) return rc;
-    return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
-                           out, cons, xy, motion, gran);
-    ABI_END
-}
-
 // ---- progressive constraints (k_prog.h; include/maxcover.h mac_prog)
 
 // mac_prog's checks, before the context is touched. *on: a constraint is present.
@@ -4865,11 +4846,10 @@ static void mads_run_prog_loop(mac_mads* m, const mac_prog* prog, double h0, dou
                 std::fill(hh, hh + K, cen[c]->h);
                 HCK(hipMemcpyAsync(d_h[c], hh, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, s));
             }
-            enqueue_eval(ctx, L, s, src, N, K, use_tiled(ctx, N, nullptr, n), L->rmax.as<double>(), m->penalty,
-                         m->d_prev, m->d_dlimT, m->d_prev ? L->dlimraw.as<double>() : nullptr, m->tan_half_fov,
-                         nullptr, L->obj.as<double>(), mads_best_ptr(m), 0, nullptr, 0, nullptr,
-                         m->d_feas.as<unsigned long long>(), m->has_cons ? &m->cons : nullptr,
-                         m->has_mot ? &m->mot : nullptr, m->xy ? nullptr : &pl);
+            EvalReq rq = mads_request(m, src, K);
+            rq.d_feas = m->d_feas.as<unsigned long long>();
+            rq.prog = m->xy ? nullptr : &pl;
+            enqueue_eval(ctx, L, s, rq);
             sa.h[c] = d_h[c];
             if (c == 0 && nc == 2) {
                 HCK(hipMemcpyAsync(L->progobj.p, L->obj.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, s));
@@ -4979,9 +4959,9 @@ int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const
     bool on = false;
     int32_t rc = prog_check(prog, three_n, &on);
     if (rc) return rc;
-    if (!on)   // no progressive constraint: the _mesh call, untouched
-        return mac_mads_run_mesh(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st,
-                                 cons, opts, motion, mesh);
+    MadsSetup su{cons, opts, motion, mesh};
+    if (!on)   // no progressive constraint: the _mesh call
+        return mads_run_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, x_out, st, su);
     if (!x0 || !x_out) return fail(MAC_E_INVAL, "null argument");
     const int N = (int)(three_n / 3);
     const double h0 = prog_h_host(x0, N, prog);
@@ -4990,15 +4970,11 @@ int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const
     const double h_max = given ? prog->h_max0 : (h0 > 0.0 ? h0 : (double)INFINITY);
     if (h0 > h_max)
         return fail(MAC_E_INVAL, "mac_prog: h(x0) = " + std::to_string(h0) + " > h_max0 = " + std::to_string(h_max));
-    const double* gran = nullptr;
-    rc = mads_mesh_check(mesh, three_n, &gran);
-    if (rc) return rc;
-    bool xy = false;
-    rc = mads_opts_check(opts, &xy);
+    rc = mads_setup_check(su, three_n);
     if (rc) return rc;
     mac_mads* m = nullptr;
     rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
-                         xy ? 4 * (three_n / 3) : 2 * three_n, &m, cons, xy, motion, gran);
+                         su.xy ? 4 * (three_n / 3) : 2 * three_n, &m, su);
     if (rc) return rc;
     try {
         set_device(ctx);

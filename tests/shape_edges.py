@@ -1,8 +1,8 @@
 """Polls on either side of every constant that routes a poll chain (tests/test_shape_edges.py checks
 the table and the generator on the CPU, tests/test_gpu_shape_edges.py runs the device over the cases).
 
-csrc/maxcover.hip enqueue_eval and the kernel headers choose kernels, launch shapes and per-thread
-layouts from K (candidates) and N (UAVs):
+csrc/eval_plan.h eval_plan (the route maxcover.hip enqueue_eval takes) and the kernel headers choose
+kernels, launch shapes and per-thread layouts from K (candidates) and N (UAVs):
 
   K < kPollMinK                  no poll chain (the per-candidate walk), unless the poll walk is forced
   K <= kFwMaxK + 1               the fused chain may run; thread 0 of fiw_kernel takes candidate kFwMaxK
@@ -64,7 +64,7 @@ ZERO_EVERY = 8        # r_max = candidate 0's radii + 0 or 1 per UAV, inside the
 #                       violations sum_i |d_i - a_i| are integers (exact), non-zero and different on
 #                       most rows; one row in ZERO_EVERY has radii == r_max (violation 0)
 WG_ALIGN = 8          # fiw_kernel, the index and the poll walk launch 8 ceil(N / 8) workgroups
-#                       (maxcover.hip enqueue_eval: nfw, nidx, pgrid: one per XCD and disk group)
+#                       (eval_plan.h: nfw, nidx; maxcover.hip pgrid: one per XCD and disk group)
 N_K = WG_ALIGN        # the N of K_EDGES and SMALL_K
 ELL = 3               # GEN_N's mesh step 2^3 = 8
 
@@ -138,8 +138,7 @@ def route(N, K, algo="auto", chain="auto", fresh=False):
     starts fused unless more than kBitsMinDisks of candidate 0's disks have neighbours).
 
     The launch roles cannot tell the 3- from the 6-per-thread index, prep_x_kernel from prep_kernel
-    or excl from its absence: there the K (or N) on each side of the constant is what crosses the
-    edge, and only the results are compared."""
+    or excl from its absence: those are asserted on the plan itself (plan below)."""
     big = N > kTiledMaxN
     chain_runs = algo == "poll" or big or K >= kPollMinK
     keys = K <= kIndexMaxKWide + 1
@@ -150,6 +149,33 @@ def route(N, K, algo="auto", chain="auto", fresh=False):
     if chain == "fused" or (fresh and N <= kBitsMinDisks):
         return True, True
     return True, None
+
+
+# mac_diag_route (csrc/maxcover.hip; host only): the plan's fields in the order it writes them
+PLAN_FIELDS = ("poll_possible", "walk_forced", "iper", "want_keys", "pair", "gen_x", "mesh", "nchain", "G",
+               "units", "fused_eligible", "excl", "counts", "prep_fused", "nprep", "xbase", "prep_five_runs",
+               "prep_five", "nrec", "nfw", "nidx", "nfin2", "nfin")
+PREP_KERNEL, PREP_X_MATRIX, PREP_X_GEN = 0, 1, 2       # eval_plan.h PrepKind
+SRC_MATRIX, SRC_BASIS, SRC_GENERATED = 0, 1, 2         # eval_plan.h RouteIn::Kind
+
+
+def plan(N, K, algo="auto", chain="auto", *, kind=SRC_MATRIX, np_=0, k0=0, mesh=False, mst=False,
+         route_five=False, b=0, delta=0.0, want_area=False, want_obj=True, cons3=False, mask=False,
+         tiled=True, cus=256, M=96 * 96, w_uniform=True):
+    """The route the library plans for one evaluation (eval_plan.h eval_plan through mac_diag_route;
+    no device): a namespace of PLAN_FIELDS. tiled: what use_tiled gives a device-resident poll."""
+    import ctypes
+    pkg = ge.load_package()
+    L = pkg.load_library()
+    L.mac_diag_route.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_double,
+                                 ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
+    L.mac_diag_route.restype = ctypes.c_int32
+    args = (pkg._lib.ALGOS[algo], pkg._lib.CHAINS[chain], cus, M, w_uniform, kind, np_, k0, mesh, mst,
+            route_five, b, want_area, want_obj, cons3, mask, tiled, N, K)
+    out = (ctypes.c_int64 * len(PLAN_FIELDS))()
+    rc = L.mac_diag_route((ctypes.c_int64 * len(args))(*(int(a) for a in args)), float(delta), out, len(out))
+    assert rc == 0, (rc, N, K)
+    return SimpleNamespace(**dict(zip(PLAN_FIELDS, (int(v) for v in out))))
 
 
 def grid_size(N):

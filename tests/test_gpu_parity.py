@@ -748,7 +748,7 @@ def test_walk_choice_scattered_batch(ctx, pkg, orc):
     """A batch that is not a poll (64 unrelated random layouts of 8 disks: no shared footprint
     across candidates) takes the per-candidate walk under AUTO; areas == exact lattice counts.
     The choice is made on the device once the neighbour lists exist; the host launches that
-    walk's kernel when the lane's recent polls chose it (maxcover.hip enqueue_eval), so a lane
+    walk's kernel when the lane's recent polls chose it (maxcover.hip enqueue_five), so a lane
     that ran poll-walk polls runs this batch once through the poll walk (same areas), records
     the choice, and takes the per-candidate walk from the next call on (the five-launch chain on
     a fresh context; AUTO there takes the fused chain, which has no walk choice: same areas)."""

@@ -13,12 +13,16 @@ takes the fp64 credit rows instead of the integer counts (weights from {1, 2, 4,
 sum exact).
 
 Which launches ran is read back from the profile and compared with shape_edges.route, the
-restatement of maxcover.hip enqueue_eval's conditions: the fused chain (fiw_kernel, fin2_kernel) or
+restatement of eval_plan.h eval_plan's conditions: the fused chain (fiw_kernel, fin2_kernel) or
 the five-launch one (disk_index_kernel, coverage_poll_kernel), or no chain at all. The roles cannot
 tell the 3- from the 6-per-thread index, prep_x_kernel from prep_kernel, or a walk that leaves cons3
-failures out from one that evaluates them: there nothing is asserted about the route, and the K (or
-N) on each side of the constant is what crosses the edge.
+failures out from one that evaluates them: those are asserted on the plan itself on the CPU
+(test_shape_edges.py, through mac_diag_route), and test_launch_sizes_are_the_plan_s ties the plan to
+the launches by their workgroup counts; here the K (or N) on each side of the constant is what
+crosses the edge.
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -152,6 +156,48 @@ def test_k_edges_auto(pkg, orc, K):
     """AUTO on a fresh context: its first poll takes the fused chain from kPollMinK to kFwMaxK + 1
     (8 disks cannot seed the history as crowded), no chain at 63, the five-launch one above."""
     _auto(pkg, orc, se.N_K, K, K in se.K_WEIGHTED)
+
+
+def _role_slots(pkg, ctx):
+    """{launch role: workgroups that took stamps} of the launches recorded since the last reset
+    (the host-only mac_diag_role_slots)."""
+    L = ctx._L
+    L.mac_diag_role_slots.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
+    L.mac_diag_role_slots.restype = ctypes.c_int32
+    roles = pkg._lib.PROF_ROLES
+    out = (ctypes.c_int64 * len(roles))()
+    assert L.mac_diag_role_slots(ctx._h, out, len(roles)) == 0
+    return {name: int(out[r]) for r, name in enumerate(roles)}
+
+
+@pytest.mark.parametrize("chain", CHAINS)
+@pytest.mark.parametrize("K", [63, 64, 3073, 3074, 6146])
+def test_launch_sizes_are_the_plan_s(pkg, ctx, orc, K, chain):
+    """The route plan (eval_plan through mac_diag_route, asserted against the table on the CPU) is what
+    was launched: the workgroups of the chain's first, index / fiw_kernel and last launch."""
+    N = se.N_K
+    c, e = _ref(orc, N, K)
+    try:
+        ctx.set_points(c.x, c.y, c.w)
+        ctx.set_chain(chain)
+        ctx.profile(True)
+        ctx.profile_read(reset=True)
+        got = ctx.area_batch(c.C)
+        slots = _role_slots(pkg, ctx)
+    finally:
+        ctx.profile_read(reset=True)
+        _reset(ctx)
+    assert np.array_equal(got, e.area)
+    p = se.plan(N, K, "auto", chain, want_area=True, want_obj=False, M=c.x.size, w_uniform=True)
+    if p.fused_eligible:      # (forced: the routing history has no say)
+        want = {"prep_kernel": p.nprep, "fiw_kernel": p.nfw, "fin2_kernel": p.nfin2}
+    elif p.poll_possible:
+        want = {"prep_kernel": p.nrec, "disk_index_kernel": p.nidx, "finalize_kernel": p.nfin}
+    else:
+        want = {}
+    assert bool(p.fused_eligible) == (chain == "fused" and 64 <= K <= 3073), (K, chain)
+    for role in ("prep_kernel", "disk_index_kernel", "finalize_kernel", "fiw_kernel", "fin2_kernel"):
+        assert slots[role] == want.get(role, 0), (K, chain, role, slots, vars(p))
 
 
 @pytest.mark.parametrize("chain", CHAINS)

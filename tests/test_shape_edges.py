@@ -75,7 +75,7 @@ def test_shapes_sit_on_the_edges():
     # (prep_x_kernel from K = 6, 12, 18, 24, 30 on; prep_kernel again from 8, 15, 22, 29 on, where
     # K mod 6 exceeds K div 6; every K >= 30 takes prep_x_kernel)
     assert flips == [6, 8, 12, 15, 18, 22, 24, 29, 30] and all(se.xk(K) for K in range(30, 300)), flips
-    # the generated-source layouts (maxcover.hip enqueue_eval: gen_x, pair)
+    # the generated-source layouts (eval_plan.h eval_plan: gen_x, pair)
     lay = [("gen_x" if N <= se.kPrepU else "pair" if (3 * N) % 4 == 0 else "chains") for N, _ in se.GEN_N]
     assert lay == ["gen_x"] * 4 + ["chains", "pair"]
     assert (3 * 14) % 4 != 0 and 6 * 513 > se.kFwMaxK + 1
@@ -90,6 +90,112 @@ def test_shapes_sit_on_the_edges():
     assert se.route(2048, 70, "tiled", "fused") == (True, False)
     assert se.route(2049, 70, "tiled", "fused") == (True, True)
     assert se.route(2049, 1, "auto", "fused") == (True, True)
+
+
+# ---------------------------------------------------------------------------- the route plan
+
+def _table_shapes():
+    """(N, K) of every K_EDGES, SMALL_K and N_EDGES shape."""
+    return ([(se.N_K, K) for K, _ in se.K_EDGES] + [(se.N_K, K) for K in se.SMALL_K]
+            + [(N, se.K_FOR_N) for N, _ in se.N_EDGES])
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def test_plan_equals_the_table_for_matrix_polls():
+    """eval_plan (through mac_diag_route) at every table shape under every algorithm and chain option:
+    what the launch roles cannot show (the index's candidates per thread, the fused prep's kernel, the
+    launch sizes) against the table's own arithmetic."""
+    for N, K in _table_shapes():
+        for algo in ("auto", "tiled", "poll"):
+            for chain in ("auto", "fused", "five"):
+                p = se.plan(N, K, algo, chain)
+                tag = (N, K, algo, chain, vars(p))
+                runs, fiw = se.route(N, K, algo, chain)
+                assert bool(p.poll_possible) == runs, tag
+                assert bool(p.fused_eligible) == (fiw is not False), tag
+                iper = 3 if K <= se.kIndexMaxK + 1 else 6 if K <= se.kIndexMaxKWide + 1 else 0
+                assert p.iper == iper and bool(p.want_keys) == (runs and iper != 0), tag
+                assert p.nfw == p.nidx == se.WG_ALIGN * _ceil(N, se.WG_ALIGN), tag
+                assert p.nfin2 == 8 * _ceil(K, 8 * se.kF2C), tag
+                assert (p.pair, p.gen_x, p.mesh) == (0, 0, 0), tag
+                assert p.nchain == _ceil(K, se.kPrepC), tag
+                x = se.xk(K, N)
+                assert p.prep_fused == (se.PREP_X_MATRIX if x else se.PREP_KERNEL), tag
+                assert p.nprep == (K // se.kPrepCX if x else _ceil(K, se.kPrepC)), tag
+                assert p.xbase == K // se.kPrepCX * se.kPrepCX, tag
+                assert (p.prep_five, p.nrec) == (se.PREP_KERNEL, _ceil(K, se.kPrepC)), tag
+                assert p.counts == (1 if runs else 0), tag
+    assert [K for K in se.SMALL_K[1:]
+            if se.plan(se.N_K, K, "poll").prep_fused != se.plan(se.N_K, K - 1, "poll").prep_fused] \
+        == [6, 8, 12, 15, 18, 22, 24, 29, 30]
+    assert [se.plan(se.N_K, K).iper for K in (3073, 3074, 6145, 6146)] == [3, 6, 6, 0]
+    assert se.plan(se.N_K, 70, w_uniform=False).counts == 0
+
+
+def test_plan_forces_the_walk_at_the_lds_limit():
+    """algo="tiled" is honoured at N = kTiledMaxN and becomes the poll walk one disk above."""
+    K = se.K_FOR_N
+    poll, tiled = se.plan(8, K, "poll").walk_forced, se.plan(se.kTiledMaxN, K, "tiled").walk_forced
+    assert poll != 0 and tiled != 0 and poll != tiled
+    assert se.plan(se.kTiledMaxN, K, "auto").walk_forced == 0
+    for algo in ("auto", "tiled", "poll"):
+        assert se.plan(se.kTiledMaxN + 1, K, algo).walk_forced == poll, algo
+        assert se.plan(se.kTiledMaxN + 1, 1, algo).poll_possible == 1, algo
+    assert se.plan(se.kTiledMaxN, K, "tiled", "fused").fused_eligible == 0
+    assert se.plan(se.kTiledMaxN + 1, K, "tiled", "fused").fused_eligible == 1
+
+
+def test_plan_leaves_failures_out_of_the_walk_up_to_kPrepU():
+    """excl: objectives-only requests with cons3 or a mask byte, N <= kPrepU."""
+    for N, _ in se.N_EDGES:
+        for want_area in (False, True):
+            for want_obj in (False, True):
+                for cons3 in (False, True):
+                    for mask in (False, True):
+                        p = se.plan(N, se.K_FOR_N, want_area=want_area, want_obj=want_obj, cons3=cons3, mask=mask)
+                        want = want_obj and (cons3 or mask) and not want_area and N <= se.kPrepU
+                        assert bool(p.excl) == want, (N, want_area, want_obj, cons3, mask)
+    assert se.plan(se.kPrepU, se.K_FOR_N, cons3=True).excl == 1
+    assert se.plan(se.kPrepU + 1, se.K_FOR_N, cons3=True).excl == 0
+
+
+def test_plan_generated_layouts():
+    """GEN_N as a generated source and in basis form (K = 6N at mesh step 8): gen_x up to kPrepU, then
+    prep_kernel by candidates or by pairs; an xy-only poll (K = 4N) never takes gen_x; a step above 8
+    keeps a poll the host can size out of the fused chain unless it is forced."""
+    lay = ["gen_x", "gen_x", "gen_x", "gen_x", "chains", "pair"]
+    for (N, _), want in zip(se.GEN_N, lay):
+        K, n = 6 * N, 3 * N
+        for kind in (se.SRC_GENERATED, se.SRC_BASIS):
+            for chain in ("auto", "fused", "five"):
+                p = se.plan(N, K, "auto", chain, kind=kind, b=2 ** se.ELL, delta=1.0, cons3=True)
+                tag = (N, kind, chain, vars(p))
+                assert (bool(p.gen_x), bool(p.pair and not p.gen_x)) == (want == "gen_x", want == "pair"), tag
+                assert p.nchain == (n // 4 if (n % 4 == 0) else _ceil(K, se.kPrepC)), tag
+                if want == "gen_x":
+                    assert (p.prep_fused, p.nprep) == (se.PREP_X_GEN, N), tag
+                    assert (p.prep_five, p.nrec) == (se.PREP_X_GEN, N), tag
+                else:
+                    assert (p.prep_fused, p.nprep) == (se.PREP_KERNEL, p.nchain), tag
+                    assert (p.prep_five, p.nrec) == (se.PREP_KERNEL, p.nchain), tag
+                assert bool(p.fused_eligible) == (chain != "five" and K <= se.kFwMaxK + 1), tag
+                assert bool(p.excl) == (N <= se.kPrepU), tag
+            # an xy-only poll of the same UAVs
+            q = se.plan(N, 4 * N, kind=kind, np_=2 * N, b=2 ** se.ELL, delta=1.0)
+            assert q.gen_x == 0 and bool(q.pair) == ((2 * N) % 4 == 0), (N, kind, vars(q))
+            assert q.prep_fused == se.PREP_KERNEL and q.prep_five == se.PREP_KERNEL, (N, kind, vars(q))
+    # the wide step, the host's crowding estimate and the pipelined loop's device-side step
+    N0 = se.GEN_N[0][0]
+    for kw in (dict(kind=se.SRC_GENERATED, b=16), dict(kind=se.SRC_BASIS, b=8, delta=1.5),
+               dict(kind=se.SRC_GENERATED, b=8, route_five=True)):
+        assert se.plan(N0, 6 * N0, **kw).fused_eligible == 0, kw
+        assert se.plan(N0, 6 * N0, "auto", "fused", **kw).fused_eligible == 1, kw
+    assert se.plan(N0, 6 * N0, kind=se.SRC_GENERATED, b=16, mst=True).fused_eligible == 1
+    assert se.plan(N0, 6 * N0, kind=se.SRC_GENERATED, b=8, mesh=True).mesh == 1
+    assert se.plan(N0, 6 * N0, kind=se.SRC_GENERATED, b=8, k0=1).gen_x == 0
 
 
 # ---------------------------------------------------------------------------- the cases
