@@ -4756,6 +4756,31 @@ static uint64_t* prog_take_ts(mac_ctx* ctx, int role, int64_t nwg)
     return ts;
 }
 
+constexpr int64_t kProgSelDiagMaxK = 1 << 20;   // mac_diag_prog_select's bound on K
+
+// prog_select_kernel's launch: one workgroup over the (objective, h) arrays of up to two centres, K
+// device doubles each (a centre that was not polled: null), the incumbents' scalars by value, the
+// record into d_rec. The loop below and mac_diag_prog_select both launch through here.
+static void prog_select_launch(hipStream_t s, uint64_t* ts, const double* const obj[2], const double* const h[2],
+                               int K, bool has_F, bool has_I, double F_f, double I_f, double I_h, double h_max,
+                               ProgRec* d_rec)
+{
+    ProgSelArgs sa{};
+    for (int c = 0; c < 2; ++c) {
+        sa.obj[c] = obj[c];
+        sa.h[c] = h[c];
+    }
+    sa.K = K;
+    sa.has_F = has_F ? 1 : 0;
+    sa.has_I = has_I ? 1 : 0;
+    sa.F_f = F_f;
+    sa.I_f = I_f;
+    sa.I_h = I_h;
+    sa.h_max = h_max;
+    hipLaunchKernelGGL(prog_select_kernel, dim3(1), dim3(kProgSelBlock), 0, s, ts, sa, d_rec);
+    HCK(hipGetLastError());
+}
+
 // The progressive barrier's loop (the rule: DESIGN.md section 4), stepped by the host from the
 // stepper's pieces. Per iteration: one basis; per centre (F, then I) the staging copy, the mask
 // launch (if any), prog_h_kernel and the poll chain on the stepper's stream, the first centre's
@@ -4815,8 +4840,8 @@ static void mads_run_prog_loop(mac_mads* m, const mac_prog* prog, double h0, dou
         if (F.has) cen[nc++] = &F;
         if (I.has) cen[nc++] = &I;
         if (nc == 2) ++two;
-        ProgSelArgs sa{};
-        sa.K = K;
+        const double* sel_obj[2] = {nullptr, nullptr};   // (a centre cons3 rejected whole stays null)
+        const double* sel_h[2] = {nullptr, nullptr};
         for (int c = 0; c < nc; ++c) {
             m->evals += K;
             if (poll_rejected(m, b, cen[c]->x.data())) {   // cons3 rejects the whole poll: no launch
@@ -4850,23 +4875,16 @@ static void mads_run_prog_loop(mac_mads* m, const mac_prog* prog, double h0, dou
             rq.d_feas = m->d_feas.as<unsigned long long>();
             rq.prog = m->xy ? nullptr : &pl;
             enqueue_eval(ctx, L, s, rq);
-            sa.h[c] = d_h[c];
+            sel_h[c] = d_h[c];
             if (c == 0 && nc == 2) {
                 HCK(hipMemcpyAsync(L->progobj.p, L->obj.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToDevice, s));
-                sa.obj[c] = L->progobj.as<double>();
+                sel_obj[c] = L->progobj.as<double>();
             } else {
-                sa.obj[c] = L->obj.as<double>();
+                sel_obj[c] = L->obj.as<double>();
             }
         }
-        sa.has_F = F.has ? 1 : 0;
-        sa.has_I = I.has ? 1 : 0;
-        sa.F_f = F.f;
-        sa.I_f = I.f;
-        sa.I_h = I.h;
-        sa.h_max = h_max;
-        hipLaunchKernelGGL(prog_select_kernel, dim3(1), dim3(kProgSelBlock), 0, s,
-                           prog_take_ts(ctx, kRoleProgSel, 1), sa, L->progrec.as<ProgRec>());
-        HCK(hipGetLastError());
+        prog_select_launch(s, prog_take_ts(ctx, kRoleProgSel, 1), sel_obj, sel_h, K, F.has, I.has, F.f, I.f, I.h,
+                           h_max, L->progrec.as<ProgRec>());
         HCK(hipMemcpyAsync(h_rec, L->progrec.p, sizeof(ProgRec), hipMemcpyDeviceToHost, s));
         const auto tb = clk::now();
         if (m->it < m->prm.n_iter) {   // the next iteration's permutations, while the device works
@@ -4947,6 +4965,52 @@ static void mads_run_prog_loop(mac_mads* m, const mac_prog* prog, double h0, dou
         ps->two_centre_polls = two;
         ps->evaluated = evaluated;
     }
+}
+
+// host only, every build (not declared in maxcover.h): prog_select_kernel on given arrays, through
+// the loop's own launch. Centre c: K host doubles of objectives and of h, or both null (the centre
+// was not polled); rec8: the 64-byte ProgRec as the kernel wrote it.
+int32_t mac_diag_prog_select(mac_ctx* ctx, const double* obj0, const double* h0, const double* obj1,
+                             const double* h1, int64_t K, int32_t has_F, int32_t has_I, double F_f, double I_f,
+                             double I_h, double h_max, int64_t* rec8)
+{
+    ABI_BEGIN
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (!rec8) return fail(MAC_E_INVAL, "null record");
+    if (K < 1 || K > kProgSelDiagMaxK)   // (the loop's K is 2 n_p <= 6 kProgMaxN)
+        return fail(MAC_E_INVAL, "mac_diag_prog_select: K = " + std::to_string(K) + " outside [1, " +
+                                     std::to_string(kProgSelDiagMaxK) + "]");
+    if ((obj0 == nullptr) != (h0 == nullptr) || (obj1 == nullptr) != (h1 == nullptr))
+        return fail(MAC_E_INVAL, "mac_diag_prog_select: a centre's objectives given without its h, or its h alone");
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t kb = sizeof(double) * (size_t)K;
+    L->progobj.reserve(2 * kb);
+    L->progh.reserve(2 * kb);
+    L->progrec.reserve(sizeof(ProgRec));
+    const double* src_obj[2] = {obj0, obj1};
+    const double* src_h[2] = {h0, h1};
+    const double* d_obj[2] = {nullptr, nullptr};
+    const double* d_h[2] = {nullptr, nullptr};
+    for (int c = 0; c < 2; ++c) {
+        if (!src_obj[c]) continue;
+        double* po = L->progobj.as<double>() + (size_t)c * (size_t)K;
+        double* ph = L->progh.as<double>() + (size_t)c * (size_t)K;
+        HCK(hipMemcpyAsync(po, src_obj[c], kb, hipMemcpyHostToDevice, s));
+        HCK(hipMemcpyAsync(ph, src_h[c], kb, hipMemcpyHostToDevice, s));
+        d_obj[c] = po;
+        d_h[c] = ph;
+    }
+    prog_select_launch(s, nullptr, d_obj, d_h, (int)K, has_F != 0, has_I != 0, F_f, I_f, I_h, h_max,
+                       L->progrec.as<ProgRec>());
+    ProgRec r;
+    HCK(hipMemcpyAsync(&r, L->progrec.p, sizeof(ProgRec), hipMemcpyDeviceToHost, s));
+    HCK(hipStreamSynchronize(s));
+    std::memcpy(rec8, &r, sizeof(ProgRec));
+    return MAC_OK;
+    ABI_END
 }
 
 int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,

@@ -2,7 +2,9 @@
 Context.prog_h against the host's h bit for bit; ctx.mads_run(prog=) (mac_mads_run_prog: prog_h_kernel
 in front of every poll chain, prog_select_kernel after them) against TDM_STATIC_opt.mads(cons_prog=)
 over the oracle's objective, iterate for iterate; prog=None / n_cons = 0 is the call without it; three
-Simulation steps against a host replay. Every comparison is exact."""
+Simulation steps against a host replay; prog_select_kernel alone on given arrays (mac_diag_prog_select)
+against the rule written out in tests/prog_cases.py; the loop at N = 22 .. 600 against the host rule
+over the device's own matrix poll. Every comparison is exact."""
 import math
 import os
 
@@ -160,9 +162,18 @@ def _mode(ctx, mode):
 def _run(ctx, pkg, orc, mode, N, radii, two=False, cons3=True, swarm_d=None, gran=None, poll_vars="xyr",
          h_max0=None, profile=False):
     res, rec, x0, r_max, c3 = _reference(pkg, orc, N, radii, two, cons3, swarm_d, gran, poll_vars, h_max0)
+    return _run_against(ctx, pkg, mode, res, rec, x0, r_max, c3 if cons3 else None, two, swarm_d, gran, poll_vars,
+                        h_max0, profile, NATIVE)
+
+
+def _run_against(ctx, pkg, mode, res, rec, x0, r_max, c3, two=False, swarm_d=None, gran=None, poll_vars="xyr",
+                 h_max0=None, profile=False, native=None):
+    """ctx.mads_run(prog=) on (rec, x0, r_max) against the host run ``res`` of the same call: the
+    whole list of what the two must share."""
+    N = x0.size // 3
     mp, plain = pkg.TDM_Constraints.merge_mac_prog(_progs(pkg, N, r_max, two))
     assert not plain
-    kw = dict(prev=c3.prev, d_lim=c3.d_lim, tan_half_fov=c3.tan_half_fov) if cons3 else {}
+    kw = dict(prev=c3.prev, d_lim=c3.d_lim, tan_half_fov=c3.tan_half_fov) if c3 is not None else {}
     if swarm_d:
         kw["cons"] = {"d_sep": swarm_d}
     ctx.set_points_records(rec)
@@ -173,7 +184,7 @@ def _run(ctx, pkg, orc, mode, N, radii, two=False, cons3=True, swarm_d=None, gra
         ctx.profile_read(reset=True)
     try:
         xn, st = ctx.mads_run(x0, r_max, 0.0, prog=mp, h_max0=h_max0, granularity=gran, poll_vars=poll_vars,
-                              **kw, **NATIVE)
+                              **kw, **(native or NATIVE))
         if profile:
             kern = {k: n for k, (ms, n) in ctx.profile_kernels().items() if n}
     finally:
@@ -208,7 +219,10 @@ def _run(ctx, pkg, orc, mode, N, radii, two=False, cons3=True, swarm_d=None, gra
 @pytest.mark.parametrize("N", [3, 12])
 def test_mads_run_prog_matches_the_host_rule(ctx, pkg, orc, N, radii, mode):
     """N = 3 (K = 18: below the poll chain) and N = 12 (K = 72: the chains), with cons3, one
-    constraint over every UAV; the launches: one prog_h per polled centre, one select per iteration."""
+    constraint over every UAV; the launches: one prog_h per polled centre, one select per iteration.
+    2K <= 144 here: no thread of prog_select_kernel takes a second trip through its stride loop and
+    its fourth wave holds no candidate; test_select_kernel_matches_the_rule and
+    test_larger_n_run_against_the_host_rule cover the strides."""
     res, st, kern = _run(ctx, pkg, orc, mode, N, radii, profile=True)
     s = res.status
     assert s.dominating >= 1 and s.unsuccessful >= 1
@@ -279,6 +293,106 @@ def test_no_prog_is_the_call_without_it(ctx, pkg, orc, N):
             {k: v for k, v in base[1].items() if k not in timing}
     with pytest.raises(ValueError, match="prog"):
         ctx.mads_stepper(x0, r_max, prog=dict(member=np.ones(N, dtype=np.uint32), limit=r_max, n_cons=1))
+
+
+# ---------------------------------------------------------------- prog_select_kernel alone
+
+@pytest.mark.parametrize("K", list(pc.SELECT_KS) + ["hand"])
+def test_select_kernel_matches_the_rule(ctx, pkg, K):
+    """Every case of prog_cases.select_cases() with this K (the hand-written ones under "hand")
+    through mac_diag_prog_select, which launches prog_select_kernel as the loop does: all eight words
+    of the record equal the rule written out (pinned against TDM_STATIC_opt.prog_select in
+    tests/test_prog_host.py); a hand-written case also states its record. 2K <= 256: one stride trip;
+    above: several, up to 52 at K = 6600; K = 63 .. 257 put the centres' border on each side of a
+    wave's and of the workgroup's end."""
+    cases = [c for c in pc.select_cases() if (c["want"] is not None) == (K == "hand") and K in ("hand", c["K"])]
+    assert len(cases) >= 13
+    for c in cases:
+        want = pc.select_written_out(*pc.rule_args(c), c["obj"], c["h"], c["K"])
+        if c["want"] is not None:
+            assert pc.record_bytes(c["want"]) == pc.record_bytes(want), c["name"]
+        got = pc.diag_prog_select(pkg, ctx, c["obj"], c["h"], c["K"], c["has_F"], c["has_I"], c["F_f"], c["I_f"],
+                                  c["I_h"], c["h_max"])
+        assert pc.record_bytes(got) == pc.record_bytes(want), (c["name"], got, want)
+
+
+def test_select_diag_errors(ctx, pkg):
+    E = pkg._lib.MAC_E_INVAL
+    a = np.zeros(4)
+    args = (1, 1, 0.0, 0.0, 1.0, 1.0)
+
+    def rc(c, obj, h, K):
+        return pc.diag_prog_select(pkg, c, obj, h, K, *args, check=False)
+
+    assert rc(None, [a, None], [a, None], 4) == E                        # a null context
+    for K in (0, -1, (1 << 20) + 1):                                     # K outside [1, 2^20]
+        assert rc(ctx, [a, None], [a, None], K) == E
+    assert rc(ctx, [a, None], [None, None], 4) == E                      # objectives without h
+    assert rc(ctx, [None, None], [a, None], 4) == E                      # h without objectives
+    assert rc(ctx, [a, a], [a, None], 4) == E and rc(ctx, [a, None], [a, a], 4) == E
+    assert rc(ctx, [a, None], [a, None], 4) == 0 and rc(ctx, [None, a], [None, a], 4) == 0
+    assert pc.diag_prog_select(pkg, ctx, [None, None], [None, None], 4, *args) == (2, math.inf, -1, 0.0, 1.0, -2, 1.0, 0)
+
+
+# ---------------------------------------------------------------- the loop at N > 12
+
+class _MatrixPollObjective:
+    """The host run's objective: the device's matrix poll on a second context (penalty as the native
+    run's), with .poll and .ctx so that TDM_STATIC_opt.mads_prog takes its objectives from
+    Context.poll_best and its h from Context.prog_h."""
+
+    def __init__(self, ctx2, r_max, penalty):
+        self.ctx, self.r_max, self.penalty = ctx2, r_max, penalty
+
+    def poll(self, X, *unused):
+        return self.ctx.poll_best(np.asarray(X, dtype=np.float64), self.r_max, self.penalty, want_all=True)
+
+    def __call__(self, v):
+        return float(self.poll(np.asarray(v, dtype=np.float64)[None, :])[2][0])
+
+
+@pytest.fixture(scope="module")
+def ctx2(pkg, ctx):
+    c = pkg.Context(0)
+    yield c
+    c.close()
+
+
+def larger_n_mirror(pkg, ctx2, N, start, **over):
+    """(res, rec, x0, r_max, c3, native kwargs): TDM_STATIC_opt.mads(cons_prog=) on the recipe."""
+    TS, TC = pkg.TDM_STATIC_opt, pkg.TDM_Constraints
+    rec, x0, r_max, kw = pc.larger_n_recipe(pkg, N, start, **over)
+    c3 = TC.create_cons3(x0, pc.FOV, np.full(N, 10.0))
+    ctx2.set_points_records(rec)
+    res = TS.mads(x0, _MatrixPollObjective(ctx2, r_max, 0.0), [pc.rowwise_cons3(c3)],
+                  cons_prog=_progs(pkg, N, r_max, False), **kw)
+    native = dict(n_iter=kw["N_iter"], ell0=kw["ell0"], ell_max=kw["ell_max"], seed=kw["seed"])
+    return res, rec, x0, r_max, c3, native
+
+
+@pytest.mark.parametrize("N,start", [(22, "mixed"), (43, "mixed"), (512, "mixed"), (512, "readme"), (600, "mixed")],
+                         ids=["22", "43", "512", "512-readme", "600"])
+def test_larger_n_run_against_the_host_rule(ctx, ctx2, pkg, N, start):
+    """ctx.mads_run(prog=) against TDM_STATIC_opt.mads(cons_prog=) at the sizes the small runs leave
+    out: N = 22 (2K = 264: a thread's second trip through prog_select_kernel's stride loop), 43
+    (K = 258: one centre alone passes the workgroup), 512 (K = 3072, the README's size, prep_x's
+    generated layout) and 600 (two UAV blocks in the prep and in prog_h_kernel: a dropped candidate is
+    evaluated and then +inf; the wide index). The host run takes its objectives from the device's
+    matrix poll on a second context and its h from Context.prog_h, so for f and h this is the build
+    against itself (both are pinned elsewhere: against the oracle, and against the host fold in
+    test_prog_h_matches_the_host): size coverage for them, and an independent check of prog_h_kernel
+    on a generated source, of the mask AND, of the loop and of prog_select_kernel, whose rule the host
+    runs in Python. _run_against's whole list, feasible_evaluations == evaluated included."""
+    res, rec, x0, r_max, c3, native = larger_n_mirror(pkg, ctx2, N, start)
+    s = res.status
+    if start == "mixed":   # (the reference side: the run is no trivial one)
+        assert s.two_centre_polls >= 1 and s.dominating >= 1 and s.improving + s.unsuccessful >= 1, vars(s)
+        assert res.x is not None
+    else:
+        h0 = pkg.TDM_Constraints.prog_h([c(x0) for c in _progs(pkg, N, r_max, False)])
+        assert res.x is None and s.two_centre_polls == 0 and s.improving >= 1 and res.h_max < h0, vars(s)
+    assert 0 < s.evaluated < s.function_evaluations - 1   # some candidates were dropped, some not
+    _run_against(ctx, pkg, "auto", res, rec, x0, r_max, c3, native=native)
 
 
 # ---------------------------------------------------------------- Simulation

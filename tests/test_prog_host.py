@@ -182,3 +182,118 @@ def test_optimize_passes_cons_prog_on(pkg, orc):
     assert got.tobytes() == (want.x if want.x is not None else want.i).tobytes()
     plain = TS.mads(x0, obj, [], 10)
     assert got.tobytes() != plain.x.tobytes()   # (penalty 0: without the constraint the radii grow)
+
+
+# ---------------------------------------------------------------- steps 3-7 alone (prog_select_kernel's cases)
+
+def _reference_record(pkg, case):
+    """TDM_STATIC_opt.prog_select on a case, its tuple mapped to ProgRec's eight fields. The count is
+    the arrays' own (prog_select takes the evaluated points and counts nothing); the best feasible
+    candidate that does not improve comes from a second call without an F, which returns it."""
+    TS = pkg.TDM_STATIC_opt
+    K = case["K"]
+    cands, evaluated = [], 0
+    for c in (0, 1):
+        if case["obj"][c] is None:
+            continue
+        f, h = case["obj"][c], case["h"][c]
+        evaluated += int(np.count_nonzero(f != math.inf))
+        cands += [(float(f[k]), float(h[k]), c, int(k)) for k in np.flatnonzero(f != math.inf)]
+    F_f, I_f, I_h, h_max = pc.rule_args(case)
+    outcome, bestF, newI, h_new = TS.prog_select(F_f, I_f, I_h, h_max, cands)
+    any_F = TS.prog_select(None, I_f, I_h, h_max, cands)[1]
+    assert bestF is None or bestF == any_F
+    code = {"dominating": 0, "improving": 1, "unsuccessful": 2}[outcome] | (pc.REPLACES_F if bestF is not None else 0)
+    bf = (math.inf, -1) if any_F is None else (any_F[0], any_F[1] * K + any_F[2])
+    if newI is None:
+        ni = (math.inf, math.inf, pc.NEW_I_NONE)
+    elif newI == "old":
+        ni = (I_f, I_h, pc.NEW_I_OLD)
+    else:
+        ni = (newI[0], newI[1], newI[2] * K + newI[3])
+    return (code, bf[0], bf[1], ni[0], ni[1], ni[2], h_new, evaluated)
+
+
+def _reference_records(pkg):
+    if "select" not in _cache:
+        _cache["select"] = [_reference_record(pkg, c) for c in pc.select_cases()]
+    return _cache["select"]
+
+
+def test_select_written_out_against_prog_select(pkg):
+    """Every case of prog_cases.select_cases(): the rule written out one candidate at a time gives the
+    record TDM_STATIC_opt.prog_select gives, field for field; a hand-written case also states it."""
+    cases = pc.select_cases()
+    assert cases is pc.select_cases() and len({c["name"] for c in cases}) == len(cases)
+    hand = 0
+    for case, ref in zip(cases, _reference_records(pkg)):
+        got = pc.select_written_out(*pc.rule_args(case), case["obj"], case["h"], case["K"])
+        assert pc.record_bytes(got) == pc.record_bytes(ref), (case["name"], got, ref)
+        if case["want"] is not None:
+            hand += 1
+            assert pc.record_bytes(case["want"]) == pc.record_bytes(ref), (case["name"], case["want"], ref)
+    assert hand >= 13
+
+
+def test_select_cases_reach_every_class(pkg):
+    """Counted on the reference's records alone: at least 20 cases of each outcome and of each kind
+    of new I, every K x centres combination, every (has_F, has_I) but neither, and the edge values."""
+    cases, recs = pc.select_cases(), _reference_records(pkg)
+    n = dict(dom_F=0, dom_I=0, improving=0, unsuccessful=0, I_cand=0, I_old=0, I_none=0)
+    for r in recs:
+        kind = r[0] & 255
+        n["dom_F"] += kind == 0 and bool(r[0] & pc.REPLACES_F)
+        n["dom_I"] += kind == 0 and not r[0] & pc.REPLACES_F
+        n["improving"] += kind == 1
+        n["unsuccessful"] += kind == 2
+        n["I_cand"] += r[5] >= 0
+        n["I_old"] += r[5] == pc.NEW_I_OLD
+        n["I_none"] += r[5] == pc.NEW_I_NONE
+    assert all(v >= 20 for v in n.values()), n
+    assert {(c["K"], c["centres"]) for c in cases} >= {(K, ce) for K in pc.SELECT_KS for ce in pc.CENTRES}
+    assert {(c["has_F"], c["has_I"]) for c in cases} == {(1, 0), (0, 1), (1, 1)}
+    assert any(c["has_I"] and c["I_f"] != c["I_f"] for c in cases) and any(c["F_f"] == math.inf for c in cases)
+    # the unevaluated share: none, about half, all but one or two, all
+    share = [r[7] / (c["K"] * (1 if c["centres"] != "both" else 2)) for c, r in zip(cases, recs)]
+    assert any(s == 0.0 for s in share) and any(0.0 < s <= 2 / 63 for s in share)
+    assert any(0.3 < s < 0.5 for s in share) and any(s > 0.7 for s in share)
+    # the edge values occur among the evaluated candidates: NaN f, h = 5e-324, I.h's two neighbours
+    seen = dict(nan=0, sub=0, below=0, above=0, at=0)
+    for c in cases:
+        for f, h in zip(c["obj"], c["h"]):
+            if f is None or not c["has_I"]:
+                continue
+            ev = f != math.inf
+            seen["nan"] += int(np.count_nonzero(f != f))
+            seen["sub"] += int(np.count_nonzero(ev & (h == 5e-324)))
+            seen["below"] += int(np.count_nonzero(ev & (h == np.nextafter(c["I_h"], -math.inf))))
+            seen["above"] += int(np.count_nonzero(ev & (h == np.nextafter(c["I_h"], math.inf))))
+            seen["at"] += int(np.count_nonzero(ev & (h == c["I_h"])))
+    assert all(seen.values()), seen
+
+
+def test_rowwise_cons3_is_create_cons3(pkg):
+    """prog_cases.rowwise_cons3 (the larger-N runs' cons3) gives create_cons3's verdict: rows at,
+    one ulp inside and one ulp outside the limit, in x, y and altitude, and random ones around it."""
+    TC = pkg.TDM_Constraints
+    N = 7
+    rng = np.random.default_rng(3)
+    x0 = np.concatenate([np.round(rng.uniform(100, 700, 2 * N)), np.full(N, 33.0)])
+    c3 = TC.create_cons3(x0, pc.FOV, np.full(N, 10.0))
+    fast = pc.rowwise_cons3(c3)
+    rows = [x0.copy()]
+    for v in range(3 * N):
+        step = 10.0 * (pc.TAN50 if v >= 2 * N else 1.0)
+        for d in (step, np.nextafter(step, 0.0), np.nextafter(step, 100.0), -step, 6.0, 8.0):
+            r = x0.copy()
+            r[v] += d
+            rows.append(r)
+    for i in range(N):   # (6, 8, 0) is at the limit exactly
+        r = x0.copy()
+        r[i] += 6.0
+        r[N + i] += 8.0
+        rows.append(r)
+    rows += list(x0[None, :] + np.round(rng.uniform(-7.0, 7.0, (200, 3 * N))))
+    got = [fast(r) for r in rows]
+    assert got == [c3(r) for r in rows] and min(got.count(True), got.count(False)) >= 20
+    assert fast.prev is c3.prev and fast.tan_half_fov == c3.tan_half_fov
