@@ -37,14 +37,22 @@ constexpr int kFinThreads = 1024;
 // integer sum) * w0.
 // The poll argmin (fb.best != null) is taken here too, with no launch of its own: every block
 // publishes the lexicographic minimum of its kFinC candidates and the block that arrives last
-// reduces the published minima (finalize_argmin below).
+// reduces the published minima (finalize_argmin below). The arrival is two-level: block b adds to
+// shard word b & 7, and the block that completes a shard adds to the root word. No word takes more
+// than max(grid / 8, 8) adds; with one word, every block's add queued on it and that queue was the
+// launch's tail. The reducer's loads come after every block's stores because each step is issued
+// only once the step before it in the same lane has returned: a block's shard add after its
+// stores are acknowledged (vmcnt(0)), a root add after the shard add that returned the shard's
+// last count (so after every add of that shard), the reducer's loads after the root add that
+// returned the root's last count (so after every root add).
 struct FinBest {
     double* best;          // {objective, index bits} (null: no argmin)
     uint64_t* mirror;      // mapped host slot {obj bits, index, seq, check} (may be null)
     uint64_t seq;
     int64_t idx_base;
     unsigned long long* blk;   // [gridDim.x][2] per-block minima {obj bits, index}
-    unsigned* arrive;          // arrival counter, zero between launches (the last block resets it)
+    unsigned* arrive;          // arrival words (kFinArriveWords: 8 shards + a root, a 128-B line each),
+                               // zero between launches (the reducer resets them)
     // the pipelined native MADS loop (k_prep.h MadsState): the last block also applies the poll's
     // update (mads_step); st == null: none
     MadsState* st;
@@ -138,6 +146,20 @@ __device__ __forceinline__ void mads_step(const FinBest& fb, double bo, int64_t 
     }
 }
 
+// The arrival words of finalize_argmin: kFinShards shard counters and one root counter, each on a
+// 128-B line of its own (fb.arrive: (kFinShards + 1) * kFinArriveStride words), zero between launches.
+constexpr int kFinShards = 8;
+constexpr int kFinArriveStride = 128 / (int)sizeof(unsigned);
+constexpr int kFinArriveWords = (kFinShards + 1) * kFinArriveStride;
+
+// the reducer's reset of the root and every shard, one word per lane in one store instruction
+// (every block's adds have returned by then: the reducer's root add was the last of them)
+__device__ __forceinline__ void finalize_arrive_reset(const FinBest& fb, int lane)
+{
+    if (lane <= kFinShards)
+        __hip_atomic_store(fb.arrive + lane * kFinArriveStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ void argmin_take(double& v1, int& i1, double v2, int i2)
 {
     if ((i2 >= 0) && (i1 < 0 || v2 < v1 || (v2 == v1 && i2 < i1))) {
@@ -149,8 +171,15 @@ __device__ __forceinline__ void argmin_take(double& v1, int& i1, double v2, int 
 // Wave 0 of every finalize block, lanes 0..kFinC-1 holding (o, k) of the block's candidates
 // (have: k < K). Cross-workgroup hand-off (MI355X_MICROARCH.md, inter-workgroup visibility, first
 // row of the sc1 table): lane 0 alone stores its block's minimum with 8-B agent-scope (sc1) stores,
-// waits for them (vmcnt(0)), then adds to ONE counter; the block whose add returns the last count
-// loads every minimum with sc1 loads, in the same wave. The lexicographic (objective, index)
+// waits for them (vmcnt(0)), then adds to its shard's counter (blockIdx & 7: blocks b and b + 8
+// share an XCD) and, if that add returns the shard's last count n_s - 1, n_s = (grid - s + 7) / 8,
+// to the root counter; the block whose root add returns min(grid, 8) - 1 is the reducer and loads
+// every minimum with sc1 loads, in the same wave. Order: an add to a word is performed after every
+// add whose return it follows in that word's sequence. A block issues its shard add after its
+// stores' acknowledgement, and a root add after its shard add has returned the last count, so at
+// that point every store of that shard's blocks is acknowledged; the reducer's root add returns
+// the last count after all 8 (or grid) such root adds, and its loads issue after that return: every
+// block's stores are acknowledged before the reducer's loads issue. The lexicographic (objective, index)
 // minimum is order-independent (the sequential first-best order); NaN / +inf never selected.
 // C: lanes holding the block's candidates (a power of two <= 64). Returns true in the last block.
 template <int C = kFinC, bool kXY = false, bool kMesh = false>   // (kMesh: mads_step's)
@@ -167,17 +196,28 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
 #pragma unroll
     for (int off = C / 2; off >= 1; off >>= 1)
         argmin_take(bv, bi, __shfl_xor(bv, off, kWave), __shfl_xor(bi, off, kWave));
-    unsigned old = 0;
+    unsigned last = 0;
     if (lane == 0) {
         __hip_atomic_store(fb.blk + 2 * blockIdx.x, __builtin_bit_cast(unsigned long long, bv),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(fb.blk + 2 * blockIdx.x + 1, (unsigned long long)(long long)bi,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        old = __hip_atomic_fetch_add(fb.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // two-level arrival: the shard's word first, and only the block that completes its shard
+        // goes on to the root (its second add is issued once the first has returned)
+        const unsigned grid = gridDim.x, s = blockIdx.x & (kFinShards - 1);
+        const unsigned ns = (grid - s + kFinShards - 1) / kFinShards;   // blocks of shard s (>= 1)
+        const unsigned a = __hip_atomic_fetch_add(fb.arrive + s * kFinArriveStride, 1u, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+        if (a == ns - 1) {
+            const unsigned nroot = grid < (unsigned)kFinShards ? grid : (unsigned)kFinShards;
+            const unsigned r = __hip_atomic_fetch_add(fb.arrive + kFinShards * kFinArriveStride, 1u,
+                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = r == nroot - 1;
+        }
     }
-    old = __shfl(old, 0, kWave);
-    if (old != gridDim.x - 1) return false;   // wave-uniform: not the last block
+    last = __shfl(last, 0, kWave);
+    if (!last) return false;   // wave-uniform: not the reducer
     // the pipelined MADS loop's state, loaded beside the minima (a stopped loop: no result)
     const int ell = fb.st ? fb.st->ell : 0;
     const double fcur = fb.st ? fb.st->f : 0.0;
@@ -216,7 +256,7 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
     const double bo = none ? __builtin_inf() : bv;
     const int64_t gidx = none ? (int64_t)-1 : fb.idx_base + bi;
     if (fb.st && ell < 0) {   // the loop stopped before this poll
-        if (lane == 0) __hip_atomic_store(fb.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        finalize_arrive_reset(fb, lane);
         return true;
     }
     if (fb.st) {
@@ -231,11 +271,15 @@ __device__ __forceinline__ bool finalize_argmin(const FinBest& fb, double o, int
         __hip_atomic_store(bw, __builtin_bit_cast(unsigned long long, bo), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(bw + 1, (unsigned long long)gidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(fb.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (fb.mirror) {
-            // d_best's stores acknowledged first, then the slot: plain stores to the mapped
-            // words, validated on the host by seq + check (no system-scope fence)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    finalize_arrive_reset(fb, lane);   // (with d_best's stores: one acknowledgement for all)
+    if (fb.mirror) {
+        // d_best's stores acknowledged first, then the slot: plain stores to the mapped words,
+        // validated on the host by seq + check (no system-scope fence). Lane 0's four or five
+        // stores issue back to back; one word per lane in one store instruction was tried and
+        // changed nothing (tried and reverted)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) {
             const uint64_t o = __builtin_bit_cast(uint64_t, bo);
             const uint64_t ix = (uint64_t)gidx;
             fb.mirror[0] = o;

@@ -274,6 +274,10 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
     double2 ppr[kFwR];      // the walk's first chunk of entries, loaded ahead (pjg: list index, -1 none)
     double pwr[kFwR];
     int pjg[kFwR];
+    // ... and, equal weights, each entry's row within the batch: the preload's search result, kept
+    // for staging (6 bits per round). The weighted builds have no register to spare and search again.
+    [[maybe_unused]] uint32_t plo = 0;
+    static_assert(kPollRB <= 64 && 6 * kFwR <= 32, "plo: 6 bits per staged round");
     {
         const uint32_t* krow = src.keysP + (int64_t)i * src.ldk;
         uint32_t pq[P];
@@ -479,16 +483,23 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
             lds_barrier();
             int id = incl - c;
             for (int q = 0; q < wid; ++q) id += wsum[q];
+            // slot s = ((dx + Dx) * nyd + dy + Dy) * nrd + dr + Dl: the triple once for s0 (the only
+            // divisions: the part has no integer divide), then stepped with the slot, dr carrying
+            // into dy and dy into dx
+            int dr = s0 % nrd, t2 = s0 / nrd;
+            int dy = t2 % nyd - Dy, dx = t2 / nyd - Dx;
+            dr -= Dl;
             for (int s = s0; s < s1; ++s) {
                 if (table[s]) {
-                    uint32_t wk = kDeadWord;
-                    if (s < nslot) {
-                        const int dr = s % nrd - Dl, t2 = s / nrd;
-                        const int dy = t2 % nyd - Dy, dx = t2 / nyd - Dx;
-                        wk = key_pack(dx, dy, dr);
-                    }
-                    poskey[id] = wk;
+                    poskey[id] = s < nslot ? key_pack(dx, dy, dr) : kDeadWord;
                     table[s] = id++;
+                }
+                if (++dr > Dr) {
+                    dr = -Dl;
+                    if (++dy > Dy) {
+                        dy = -Dy;
+                        ++dx;
+                    }
                 }
             }
             if (tid == kFwThreads - 1) ucnt = id;
@@ -552,6 +563,7 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
                         if (rpre[mid] <= qd) lo = mid; else hi = mid - 1;
                     }
                     pjg[r] = rs[lo] + (qd - rpre[lo]);
+                    if constexpr (kCounts) plo |= (uint32_t)lo << (6 * r);
                     ppr[r] = a.xy[pjg[r]];
                     pwr[r] = a.w[pjg[r]];
                 }
@@ -758,9 +770,13 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
                         if (qd < nraw) {
                             const int f = base + qd;
                             int lo = 0, hi = nr - 1;
-                            while (lo < hi) {
-                                const int mid = (lo + hi + 1) >> 1;
-                                if (rpre[mid] <= f) lo = mid; else hi = mid - 1;
+                            if (kCounts && pre) {   // (the row the preload's search found)
+                                lo = (int)((plo >> (6 * r)) & 63u);
+                            } else {
+                                while (lo < hi) {
+                                    const int mid = (lo + hi + 1) >> 1;
+                                    if (rpre[mid] <= f) lo = mid; else hi = mid - 1;
+                                }
                             }
                             if (pre) {
                                 jg[r] = pjg[r];

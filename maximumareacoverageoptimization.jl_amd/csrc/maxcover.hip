@@ -840,7 +840,8 @@ static FinBest fin_best(const EvalRun& r, unsigned nfin)
     FinBest fb{};
     if (!rq.d_best) return fb;
     L->finblk.reserve(2 * sizeof(unsigned long long) * nfin);
-    if (L->finarrive.grow(sizeof(unsigned)))   // zero once; the last block of each launch resets it
+    // (8 shard words and a root, a line each) zero once; the reducer of each launch resets them
+    if (L->finarrive.grow(sizeof(unsigned) * kFinArriveWords))
         HCK(hipMemsetAsync(L->finarrive.p, 0, L->finarrive.cap, r.s));
     if (rq.fb_mads) fb = *rq.fb_mads;   // the pipelined MADS loop's update fields
     fb.best = rq.d_best;
