@@ -711,6 +711,18 @@ int32_t mac_profile_kernels(mac_ctx* ctx, double* ms_out, int64_t* launches_out,
  * sum and the largest of hint word 1, the disks of a poll that took one position per candidate (keys
  * that reproduce no double: the identity map). Any output may be NULL; reset != 0 clears the three. */
 int32_t mac_profile_fused(mac_ctx* ctx, int64_t* reports, int64_t* ident_sum, int64_t* ident_max, int32_t reset);
+/* Host-only diagnostic: what decided the shared entries of the context's most recent poll on the
+ * five-launch chain. Synchronises the device, then copies back from that poll's scratch:
+ *   words[0]  the walk that ran (1 the poll walk, 2 the per-candidate walk, 0 a stopped loop);
+ *   words[1 + q], q < 9: the poll walk's counters: 0 disks with neighbours that qualify for the
+ *             bit-word kernel and the union pass, 1 and 3 job counters, 2 disks with neighbours that do
+ *             not qualify (an overflowed lower list, or a region past 64 x 64 tiles), 4..7 the union
+ *             pass's jobs per weight bucket, 8 disks whose upper list overflowed (the union pass
+ *             stands down); words past these are set to 0;
+ *   ucount[i], i < n_disks: disk i's distinct positions (the index).
+ * Pass that poll's N as n_disks (entries past it are whatever the scratch holds). MAC_E_INVAL when
+ * no such poll has run or n_disks exceeds the scratch. Launches nothing. */
+int32_t mac_diag_poll_report(mac_ctx* ctx, int32_t* words, int32_t n_words, int32_t* ucount, int32_t n_disks);
 
 /* ---- fire generator (src/DynamicArea.jl, config 5) ------------------------------ */
 /* Cellular-automaton forest fire on an nx x ny grid of dx x dy cells, cell (i, j) 1-based with

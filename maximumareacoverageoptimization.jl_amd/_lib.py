@@ -48,6 +48,10 @@ PROF_ROLES = ("prep_kernel",  # (role 0: the prep launch, prep_kernel or prep_x_
               "coverage_poll_kernel", "shared_or_kernel", "finalize_kernel", "fiw_kernel",
               "fin2_kernel", "cons_mask_gen_kernel", "prog_h_kernel", "prog_select_kernel")
 
+# mac_diag_poll_report: the poll walk's counters in their order (csrc/k_common.h kDc*)
+POLL_COUNTERS = ("bits", "poll_jobs", "other", "bits_jobs", "or_jobs0", "or_jobs1", "or_jobs2",
+                 "or_jobs3", "or_bad")
+
 ALGOS = {"auto": MAC_ALGO_AUTO, "scan": MAC_ALGO_SCAN, "tiled": MAC_ALGO_TILED,
          "poll": MAC_ALGO_POLL}
 
@@ -79,7 +83,7 @@ EXPORTS = (
     "mac_cons_mask_motion_f64", "mac_poll_best_motion_f64", "mac_motion_thresholds",
     "mac_mads_run_motion", "mac_mads_begin_motion",
     "mac_mads_run_mesh", "mac_mads_begin_mesh", "mac_profile_fused",
-    "mac_prog_h_f64", "mac_mads_run_prog",
+    "mac_prog_h_f64", "mac_mads_run_prog", "mac_diag_poll_report",
 )
 
 MAC_REGIONS_MAX = 64
@@ -381,6 +385,7 @@ def _declare(L: ctypes.CDLL) -> None:
         "mac_profile_split": ([_vp, _dp, _dp, _dp, _i64p], _i32),
         "mac_profile_kernels": ([_vp, _dp, _i64p, _i32], _i32),
         "mac_profile_fused": ([_vp, _i64p, _i64p, _i64p, _i32], _i32),
+        "mac_diag_poll_report": ([_vp, ctypes.POINTER(_i32), _i32, ctypes.POINTER(_i32), _i32], _i32),
         "mac_append_points_f64": ([_vp, _dp, _dp, _dp, _i64], _i32),
         "mac_mads_run": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                           ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats)], _i32),
@@ -675,6 +680,19 @@ class Context:
         _check(self._L.mac_profile_fused(self._h, ctypes.byref(r), ctypes.byref(s), ctypes.byref(m),
                                          1 if reset else 0))
         return {"reports": int(r.value), "ident_sum": int(s.value), "ident_max": int(m.value)}
+
+    def poll_report(self, n_disks: int) -> dict:
+        """What decided the shared entries of the context's most recent five-launch poll
+        (mac_diag_poll_report; host only, synchronises the device): the walk that ran, the poll
+        walk's counters by name (csrc/k_common.h kDc*) and the positions of each of its n_disks
+        disks."""
+        words = (_i32 * (1 + len(POLL_COUNTERS)))()
+        uc = (_i32 * max(1, int(n_disks)))()
+        _check(self._L.mac_diag_poll_report(self._h, words, len(words), uc, int(n_disks)))
+        out = {"walk": {1: "poll", 2: "tiled"}.get(int(words[0])),
+               "ucount": np.array(uc[:int(n_disks)], dtype=np.int64)}
+        out.update({name: int(words[1 + q]) for q, name in enumerate(POLL_COUNTERS)})
+        return out
 
     # -- point list
     def set_points(self, x, y, w) -> None:

@@ -57,6 +57,7 @@ constexpr int kBitsPL = 2;                          // positions per lane in the
 constexpr int kBitsBlk = kBitsPL * kWave;           // positions per wave block
 constexpr int kBitsE = 1024;                        // shared entries staged in LDS at a time
 constexpr int kBitsUC = 16384;                      // map values cached per job (uint16)
+constexpr int kBitsUCMax = 1 << 16;                 // ... of disks with at most this many positions
 
 
 // (cur << 1) | sign bit of v, one v_alignbit_b32 ({cur, v} >> 31). Written as asm: the compiler's
@@ -221,8 +222,10 @@ __global__ __launch_bounds__(kBitsThreads) void shared_bits_kernel(
             const int nrun = nruns;
             const int kend = min(K, kb + kBitsK);
             const int kc = kend - kb;
-            // the job's map values in LDS when they fit (positions < kBitsTab < 2^16)
-            const bool cached = nd * kc <= kBitsUC;
+            // the job's map values in LDS when they fit: nd * kc of them, and each one (a position
+            // within its disk, up to sU[m] - 1: K - 1 under the identity map) in 16 bits
+            bool cached = nd * kc <= kBitsUC;
+            for (int m = 0; m < nd; ++m) cached &= sU[m] <= kBitsUCMax;   // uniform
             if (cached)
                 for (int t = tid; t < nd * kc; t += kBitsThreads) {
                     const int m = t / kc, kk = t - m * kc;

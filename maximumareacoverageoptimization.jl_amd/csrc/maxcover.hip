@@ -247,6 +247,7 @@ struct mac_ctx {
     std::atomic<int64_t> cl_led{0};             // requests whose own thread led their batch
     std::vector<Lane*> lanes_free;
     std::vector<Lane*> lanes_all;
+    std::atomic<Lane*> last_five{nullptr};   // the lane of the most recent five-launch poll (mac_diag_poll_report)
     hipStream_t setup_stream = nullptr;
     // device polls' result mirror (guarded by mu): one mapped coherent slot {obj bits, index,
     // seq, check} per d_best buffer (k_final.h mirror_check), reassigned least recently used; the
@@ -1203,6 +1204,7 @@ static void enqueue_five(EvalRun& r, const CandSrc& keyed, WalkOut& w)
                        pl.walk_forced == 0 ? L->cost.as<double2>() : nullptr, kPollCostRatio);
     HCK(hipGetLastError());
     if (bits_on) enqueue_shared_pass(r, bits_on);
+    ctx->last_five.store(L, std::memory_order_relaxed);
     w.d_spart = L->spart.as<double>();
     w.d_ncount = L->ncount.as<int>();
 }
@@ -1850,6 +1852,30 @@ int32_t mac_diag_role_slots(mac_ctx* ctx, int64_t* out, int32_t n_roles)
         for (int r = 0; r < n_roles && r < MAC_PROF_ROLES; ++r)
             if (p.role[r][0] >= 0) out[r] += p.role[r][1];
     return MAC_OK;
+}
+
+// host only (declared in maxcover.h): what the context's most recent five-launch poll left on its
+// lane, copied back after a device synchronisation: words[0] the walk (k_common.h kMode*),
+// words[1 ..] the poll walk's counters (kDc*), and the index's positions per disk. Launches
+// nothing and changes nothing a poll reads.
+int32_t mac_diag_poll_report(mac_ctx* ctx, int32_t* words, int32_t n_words, int32_t* ucount, int32_t n_disks)
+{
+    ABI_BEGIN
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (n_words < 0 || n_disks < 0 || (n_words > 0 && !words) || (n_disks > 0 && !ucount))
+        return fail(MAC_E_INVAL, "mac_diag_poll_report: a count without its array");
+    set_device(ctx);
+    HCK(hipDeviceSynchronize());
+    const Lane* L = ctx->last_five.load(std::memory_order_relaxed);
+    if (!L) return fail(MAC_E_INVAL, "mac_diag_poll_report: no five-launch poll has run on this context");
+    if (sizeof(int) * (size_t)n_disks > L->ucount.cap)
+        return fail(MAC_E_INVAL, "mac_diag_poll_report: more disks than the poll had");
+    const int nw = std::min<int>(n_words, 1 + kDcCount);
+    for (int q = nw; q < n_words; ++q) words[q] = 0;
+    if (nw > 0) HCK(hipMemcpy(words, L->mode.p, sizeof(int) * (size_t)nw, hipMemcpyDeviceToHost));
+    if (n_disks > 0) HCK(hipMemcpy(ucount, L->ucount.p, sizeof(int) * (size_t)n_disks, hipMemcpyDeviceToHost));
+    return MAC_OK;
+    ABI_END
 }
 
 const char* mac_last_error(void) { return g_last_error.c_str(); }

@@ -912,10 +912,13 @@ def test_poll_walk_stress(ctx, pkg, orc, case):
 @pytest.mark.parametrize("case", ["crowded", "real_clustered", "mixed_weights", "pythagorean",
                                   "lattice_mixed"])
 def test_shared_entry_passes(ctx, pkg, orc, case):
-    """Both shared-entry passes of the poll walk, forced (MAC_OPT_SHARED): the poll kernel's fp64
-    jobs and the bit-word kernel (k_bits.h: per-position coverage words, band entries in fp64,
-    weighted credit bit by bit), each against the C oracle. "crowded": 100 disks over one square
-    (neighbour lists past 64 go to the fp64 jobs even when the bit-words are forced);
+    """The shared-entry passes of the poll walk, forced (MAC_OPT_SHARED), each against the C oracle:
+    "fp64" is the poll kernel's fp64 jobs; "bits" is, on equal weights ("crowded", "real_clustered",
+    "pythagorean"), the union pass (k_or.h shared_or_kernel: enqueue_shared_pass launches it whenever
+    the list is not weighted, and shared_route returns 2), and only on the weighted lists
+    ("mixed_weights", "lattice_mixed") the bit-word kernel (k_bits.h: per-position coverage words, band
+    entries in fp64, weighted credit bit by bit). "crowded": 100 disks over one square
+    (neighbour lists past 64: the union pass stands down and the fp64 jobs take every disk);
     "real_clustered": non-lattice coordinates (band decisions); "mixed_weights": real weights
     (rtol 1e-12, the summation order differs from the list order); "pythagorean": entries exactly
     at distance r (every one in the band, not covered); "lattice_mixed": integer weights (exact)."""
