@@ -63,6 +63,18 @@ extern "C" {
 
 #define MAC_OPT_CHAIN        6  /* the poll chain: MAC_CHAIN_AUTO (default) | _FIVE | _FUSED */
 
+#define MAC_OPT_MESH_KEYS    7  /* how the native MADS driver's polls on a mesh (mac_mads_mesh) key their disks:
+                                   MAC_KEYS_VALUE (default) | MAC_KEYS_MESH. Read when a run or a stepper
+                                   begins (mac_mads_run_mesh, mac_mads_begin_mesh, mac_mads_run_prog and what is
+                                   layered on them); a stepper keeps the mode it began with. Without a mesh
+                                   (NULL, or every granularity 1.0) the option changes nothing. Results are
+                                   the same under both; only the speed differs.        */
+
+#define MAC_KEYS_VALUE   0  /* offsets in metres from candidate 0's disk: exact at any granularity, packed
+                               (fast) at integer granularities only                                          */
+#define MAC_KEYS_MESH    1  /* the poll's signed integer draws, base the incumbent, scale the disk's
+                               granularities: every granularity packs as the unit mesh does                 */
+
 #define MAC_CHAIN_AUTO   0  /* the fused three-launch chain unless one of the context's last 64 polls was crowded,
                                scattered or off the packed-key grid (then the five-launch chain)  */
 #define MAC_CHAIN_FIVE   1  /* always the five-launch chain (prep, index, set-up, walk, finalize)   */

@@ -19,7 +19,7 @@ module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
        poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacProg, MadsProgStats, MacCons, MacMotion, cons_mask,
-       set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
+       set_mesh_keys!, set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
     joinpath(@__DIR__, "..", "maximumareacoverageoptimization.jl_amd", "libmaxcover.so"))
@@ -75,6 +75,21 @@ function set_points!(ctx::MacContext, points::AbstractVector{<:AbstractVector{Fl
     rec = pack_records(points)
     check(ccall((:mac_set_points_records_f64, libmaxcover), Int32,
                 (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64), ctx, rec, size(rec, 2), 5))
+    return ctx
+end
+
+const MAC_OPT_MESH_KEYS = Int32(7)
+
+"""
+    set_mesh_keys!(ctx, on)
+
+How `mads_run` polls on a mesh (`MacMadsMesh`) key their disks (MAC_OPT_MESH_KEYS): `false` (default) by
+offsets in metres, which pack only at integer granularities; `true` by the poll's signed integer draws,
+which pack at every granularity. Results are the same. Read when a run begins.
+"""
+function set_mesh_keys!(ctx::MacContext, on::Bool)
+    check(ccall((:mac_set_option, libmaxcover), Int32, (Ptr{Cvoid}, Int32, Int64), ctx,
+                MAC_OPT_MESH_KEYS, on ? 1 : 0))
     return ctx
 end
 

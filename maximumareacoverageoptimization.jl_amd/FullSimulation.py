@@ -150,7 +150,9 @@ class Simulation:
     with ``motion=None`` the records and calls are what they were.
     ``granularity``: the MADS mesh of every step (None, a scalar, a pair (g_xy, g_r) or 3N values:
     Context.mads_run, mac_mads_mesh), in all three modes; "auto" then compares with g_r / 2. None:
-    the calls as they were.
+    the calls as they were. ``mesh_keys``: True switches the context to keys in mesh units
+    (Context.set_mesh_keys: the same results, every granularity at the unit mesh's packed keys); False
+    (default) leaves the context's option as it is.
     ``cons_prog``: the progressive constraints MADS gets (the reference's cons_prog slot, :23, :86,
     :97), under the progressive barrier of Context.mads_run(prog=) with the first threshold
     ``h_max0`` (None: h at each step's MADS input). An entry is a constraint carrying ``mac_prog``
@@ -169,12 +171,15 @@ class Simulation:
                  shard=None, gather=None, speculate: bool | None = None, device=None,
                  attribution: bool = False, cons_ext=(), high_interest=None, w_high=None,
                  poll_vars: str = "xyr", motion=None, velocities=None, granularity=None,
-                 cons_prog=(), h_max0=None, penalty: float = 1e5):
+                 cons_prog=(), h_max0=None, penalty: float = 1e5, mesh_keys: bool = False):
         if poll_vars not in ("xyr", "xy", "auto"):
             raise ValueError(f"poll_vars must be 'xyr', 'xy' or 'auto', not {poll_vars!r}")
         self.poll_vars = poll_vars
         self.granularity = mesh_granularity(granularity, np.asarray(starting_circles).size)
         self.ctx = ctx
+        self.mesh_keys = bool(mesh_keys)
+        if self.mesh_keys:   # (Context.set_mesh_keys: read as each step's run begins)
+            ctx.set_mesh_keys(True)
         self.high_interest = self._boxes(high_interest)
         if self.high_interest is None and w_high is not None:
             raise ValueError("w_high needs high_interest")

@@ -31,6 +31,9 @@ MAC_OPT_TILE_POINTS = 3
 MAC_OPT_PROFILE = 4
 MAC_OPT_SHARED = 5
 MAC_OPT_CHAIN = 6
+MAC_OPT_MESH_KEYS = 7
+MAC_KEYS_VALUE = 0
+MAC_KEYS_MESH = 1
 SHARED_MODES = {"auto": 0, "fp64": 1, "bits": 2}
 CHAINS = {"auto": 0, "five": 1, "fused": 2}
 MAC_ALGO_AUTO = 0
@@ -633,6 +636,13 @@ class Context:
         lane's recent polls were crowded, scattered or off the packed-key grid), "five" (prep, index,
         set-up, walk, finalize) or "fused" (prep, fiw, fin2 whenever it applies)."""
         self.set_option(MAC_OPT_CHAIN, CHAINS[chain])
+
+    def set_mesh_keys(self, on: bool = True) -> None:
+        """How the native MADS driver's polls on a mesh (``mesh=`` of mads_run / mads_begin) key
+        their disks (MAC_OPT_MESH_KEYS): off (default) by their offsets in metres, which pack only at
+        integer granularities; on by the poll's signed integer draws, which pack at every granularity.
+        Results are the same; read when a run or a stepper begins (a stepper keeps its mode)."""
+        self.set_option(MAC_OPT_MESH_KEYS, MAC_KEYS_MESH if on else MAC_KEYS_VALUE)
 
     def set_algo(self, algo: str) -> None:
         if algo not in ALGOS:

@@ -55,6 +55,7 @@ struct RouteIn {
     int kind = kMatrix;
     int np = 0, k0 = 0;                    // (generated and basis-form sources: CandSrc.np, k0)
     bool mesh = false, mst = false, route_five = false;
+    bool mesh_keys = false;                // MAC_OPT_MESH_KEYS (with a mesh: the kMeshKeys builds)
     int64_t b = 0;
     double delta = 0.0;
     bool want_area = false, want_obj = false;
@@ -71,7 +72,7 @@ struct EvalPlan {
     int iper;              // candidates per index thread: 3 (K <= 3073), 6 (K <= 6145); 0: identity map
     bool want_keys;        // the index hashes the prep's packed keys
     bool pair, gen_x;      // generated complete polls: the prep's layouts (k_prep.h)
-    bool mesh;             // a generated poll on a mesh: the chains' kMesh builds
+    int mesh;              // a generated poll on a mesh: the chains' kMesh builds (1 value keys, 2 mesh keys)
     int nchain;            // prep_kernel's workgroups
     int G;                 // the per-candidate walk's slices per candidate
     int64_t units;         // ... and its (candidate, slice) units
@@ -107,7 +108,7 @@ static inline EvalPlan eval_plan(const RouteIn& in)
     p.poll_possible = poll_walk_possible(in.algo, in.M, N, K, in.tiled);
     p.iper = K <= kIndexMaxK + 1 ? kIdxPer : K <= kIndexMaxKWide + 1 ? kIdxPerWide : 0;
     p.want_keys = p.poll_possible && p.iper;
-    p.mesh = gen && in.mesh;
+    p.mesh = gen && in.mesh ? (in.mesh_keys && in.kind == RouteIn::kGenerated ? mac::kMeshKeys : 1) : 0;
     const int target = 8 * in.cus;
     p.G = (int)std::max<int64_t>(1, std::min<int64_t>((target + K - 1) / K, std::max(1, N / kWavesPerBlock)));
     p.units = (int64_t)K * p.G;

@@ -129,18 +129,48 @@ __device__ __forceinline__ DiskRec word_disk(uint32_t w, double bx, double by, d
 // generator there and keeps its operands in scalar registers through code a matrix poll never runs
 // (DESIGN.md §4 "Two instantiations per source").
 // kMesh: a generated poll on a mesh (mac_mads_mesh), likewise known at the enqueue and its own build.
-template <bool kMat, bool kMesh = false>
+template <bool kMat, int kMesh = 0>
 __device__ __forceinline__ double src_val(const CandSrc& s, int k, int v, int N)
 {
     return s.val<kMat, kMesh>(k, v, N);
 }
 
+// Mesh keys (mesh_key.h; kMesh == kMeshKeys): a word holds signed draws, its base the incumbent's disk
+// and its scale the disk's granularities, kb = {x, y, r, g_x, g_y, g_r}
+__device__ __forceinline__ DiskRec mesh_word_disk(uint32_t w, const double* kb)
+{
+    if (w == kDeadWord) return inert_disk();
+    float fx, fy, fr;
+    key_unpack(w, fx, fy, fr);
+    return make_disk(mesh_key_decode(kb[0], kb[3], (double)fx), mesh_key_decode(kb[1], kb[4], (double)fy),
+                     mesh_key_decode(kb[2], kb[5], (double)fr));
+}
+// ... of disk jj, read from the source (the incumbent and the mesh)
+__device__ __forceinline__ void mesh_key_base(const CandSrc& s, int jj, int N, double (&kb)[6])
+{
+    const double* const gm = s.mesh_ptr();
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        kb[q] = s.xinc[q * N + jj];
+        kb[3 + q] = gm[q * N + jj];
+    }
+}
+
 // Disk jj of candidate k from its key word, or the candidate's own values when the key escaped
-template <bool kMat, bool kMesh = false>
+// (bx, by, br: candidate 0's disk jj, the base of value keys; mesh keys read their own)
+template <bool kMat, int kMesh = 0>
 __device__ __forceinline__ DiskRec key_disk(const CandSrc& s, uint32_t key, int jj, int k, int N, double bx,
                                             double by, double br)
 {
-    if (key != kKeyEsc) return word_disk(key, bx, by, br);
+    if constexpr (kMesh == kMeshKeys) {
+        if (key != kKeyEsc) {
+            double kb[6];
+            mesh_key_base(s, jj, N, kb);
+            return mesh_word_disk(key, kb);
+        }
+    } else {
+        if (key != kKeyEsc) return word_disk(key, bx, by, br);
+    }
     return make_disk(src_val<kMat, kMesh>(s, k, jj, N), src_val<kMat, kMesh>(s, k, N + jj, N),
                      src_val<kMat, kMesh>(s, k, 2 * N + jj, N));
 }
@@ -199,7 +229,7 @@ template <> struct FwAcc<true> { typedef unsigned T; };
 
 // kCounts == (a.counts != 0): the equal-weight build keeps its credits in 32-bit integers (half the
 // registers of the walk's accumulators and of the shared credits)
-template <bool kCounts, bool kMat, bool kMesh = false>   // (kMesh: generated polls only)
+template <bool kCounts, bool kMat, int kMesh = 0>   // (kMesh: generated polls only)
 __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2))) void fiw_kernel(
     uint64_t* ts, FwArgs a)
 {
@@ -242,6 +272,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
     __shared__ double nb_b[kFwNbr][3];
     __shared__ double dred[kFwWaves][4];
     __shared__ double sbase[7];   // candidate 0's disk i, the displacement bound
+    // (mesh keys: the key base and scale of disk i, mesh_key_base; the other builds never touch it)
+    __shared__ double mkb[kMesh == kMeshKeys ? 6 : 1];
     __shared__ uint8_t scov[kFwKPB]; // per slice slot: its position's disk covers (finite, r > 0)
     __shared__ unsigned ninner;      // entries every position covers (the annulus, counts only)
     __shared__ int ucnt, ncnt, lslot;
@@ -373,6 +405,12 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
             sbase[4] = dmy;
             sbase[5] = dmr;
             sbase[6] = dml;
+            if constexpr (kMesh == kMeshKeys) {
+                double kb[6];
+                mesh_key_base(src, i, N, kb);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) mkb[q] = kb[q];
+            }
         }
         const bool rany = sup_box(bx, by, br, dmx, dmy, dmr, g, RG);
         if (!rany) RG = make_int4(0, -1, 0, -1);
@@ -417,7 +455,9 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
         // displacement bound): one slot per offset triple, plain stores, positions numbered in slot
         // order; a candidate whose disk has r <= 0 (covers nothing) goes to the dead slot. Else an
         // LDS hash over the key words (linear probing).
-        const bool dfits = !ident && dmx >= 0.0 && dmx <= 1023.0 && dmy >= 0.0 && dmy <= 1023.0 &&
+        // (mesh keys: the bound is in metres and the fields in mesh units, so the direct table stands
+        // down and the LDS hash numbers the words)
+        const bool dfits = kMesh != kMeshKeys && !ident && dmx >= 0.0 && dmx <= 1023.0 && dmy >= 0.0 && dmy <= 1023.0 &&
                            dmr >= -511.0 && dmr <= 511.0 && dml >= -511.0 && dml <= 511.0;
         const int Dx = dfits ? (int)dmx : 0, Dy = dfits ? (int)dmy : 0;
         const int Dr = dfits ? (int)dmr : 0, Dl = dfits ? (int)dml : 0;
@@ -632,7 +672,8 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
             return make_disk(src_val<kMat, kMesh>(src, u, i, N), src_val<kMat, kMesh>(src, u, N + i, N),
                              src_val<kMat, kMesh>(src, u, 2 * N + i, N));
         }
-        return word_disk(poskey[u], sbase[0], sbase[1], sbase[2]);
+        if constexpr (kMesh == kMeshKeys) return mesh_word_disk(poskey[u], mkb);
+        else return word_disk(poskey[u], sbase[0], sbase[1], sbase[2]);
     };
 
     // The walk's lane constants need T(r) only to within the fp32 filter's spare error budget
@@ -652,9 +693,15 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
             if (w == kDeadWord) return inert_disk();
             float fx, fy, fr;
             key_unpack(w, fx, fy, fr);
-            d.cx = sbase[0] + (double)fx;
-            d.cy = sbase[1] + (double)fy;
-            d.r = sbase[2] + (double)fr;
+            if constexpr (kMesh == kMeshKeys) {
+                d.cx = mesh_key_decode(mkb[0], mkb[3], (double)fx);
+                d.cy = mesh_key_decode(mkb[1], mkb[4], (double)fy);
+                d.r = mesh_key_decode(mkb[2], mkb[5], (double)fr);
+            } else {
+                d.cx = sbase[0] + (double)fx;
+                d.cy = sbase[1] + (double)fy;
+                d.r = sbase[2] + (double)fr;
+            }
         }
         d.T = d.r > 0.0 ? d.r * d.r : -1.0;
         return d;
@@ -1199,7 +1246,7 @@ struct F2Shared {
     const uint8_t* dead;
 };
 
-template <bool kCounts, bool kMat, bool kXY = false, bool kMesh = false>   // (kXY, kMesh: as finalize_kernel's; generated polls only)
+template <bool kCounts, bool kMat, bool kXY = false, int kMesh = 0>   // (kXY, kMesh: as finalize_kernel's; generated polls only)
 __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     const unsigned* __restrict__ crow, const double* __restrict__ frow, int ldk, int N, int K,
     double w0, const double* __restrict__ vp, double* __restrict__ area_out, double* __restrict__ obj_out,
@@ -1575,7 +1622,7 @@ __global__ __launch_bounds__(kF2Threads) void fin2_kernel(
     }
     MAC_F2_STAMP(4);
     if (fb.best && t < kWave) {
-        [[maybe_unused]] const bool last = finalize_argmin<C, kXY, kMesh>(fb, o, k, k < K);   // (+ the hint words)
+        [[maybe_unused]] const bool last = finalize_argmin<C, kXY, kMesh != 0>(fb, o, k, k < K);   // (+ the hint words)
 #ifdef MAC_DIAG
         if (t == 0 && blockIdx.x < 4096) g_diag_f2[8 * blockIdx.x + 7] = last;
 #endif

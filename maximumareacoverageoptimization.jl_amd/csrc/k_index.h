@@ -136,7 +136,7 @@ __device__ __forceinline__ float key_of(double v, double b, bool& ok)
 // kXY: an xy-only generated poll (src.np != 0), selected at compile time: the full poll's
 // instantiation is the code it was.
 // kMesh: a generated poll on a mesh (mac_mads_mesh; CandSrc.step_m), likewise its own build.
-template <bool kKeys, int kPer, bool kXY = false, bool kMesh = false>
+template <bool kKeys, int kPer, bool kXY = false, int kMesh = 0>
 __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPer <= 3 ? 8 : 4))) void disk_index_kernel(
     uint64_t* ts, CandSrc src0, int N, int K, Grid g, int dedup, IndexOut o)
 {
@@ -225,9 +225,24 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
     constexpr int P = kIdxPer + 1;
     int slot[P];
     double bx = 0.0, by = 0.0, br = 0.0;   // candidate 0's disk: the key base
+    // (mesh keys, mesh_key.h: the base is the incumbent's disk i, the scale its three granularities)
+    [[maybe_unused]] double gx = 1.0, gy = 1.0, gr = 1.0;
+    auto key_base = [&]() {
+        if constexpr (kMesh == kMeshKeys) {
+            const double* const gm = src.mesh_ptr();
+            bx = src.xinc[i];
+            by = src.xinc[N + i];
+            br = src.xinc[2 * N + i];
+            gx = gm[i];
+            gy = gm[N + i];
+            gr = gm[2 * N + i];
+        } else {
+            get3(0, bx, by, br);
+        }
+    };
     if (fits && kKeys) {
         // ---- keys: rows of the fp32 key matrix (coalesced) and the tiles' exactness flags
-        get3(0, bx, by, br);
+        key_base();
         const uint32_t* fp = src.keysP + (int64_t)i * src.ldk;
         uint32_t pq[P];
 #pragma unroll
@@ -241,7 +256,8 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             key_unpack(pq[j], qx[j], qy[j], qr[j]);
-            if (pq[j] == kKeyEsc) {
+            // (mesh keys: no fp32 rows; an escape marked the record, pbad, and the disk takes the identity map)
+            if (kMesh != kMeshKeys && pq[j] == kKeyEsc) {
                 const int k = min(j < kIdxPer ? tid + j * kIdxThreads : (tid == 0 ? kIndexMaxK : K), K - 1);
                 const float* fx = src.keysT + (int64_t)i * src.ldk;
                 qx[j] = fx[k];
@@ -278,8 +294,9 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
         hashed = !__syncthreads_or(bad);                  // (the barrier also publishes the keys)
     } else if (fits) {
         double cx[P], cy[P], cr[P];
+        [[maybe_unused]] float mx[P], my[P], mr[P];   // (mesh keys) the signed draws: the key triple
         // ---- keys: every load in flight at once, then the fp32 offsets (exactness voted)
-        get3(0, bx, by, br);
+        key_base();
         load_partials();
         const int n = 3 * N;
         // (a full poll's: an xy-only poll reads its candidates through src.get)
@@ -301,7 +318,7 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
             // (a mesh, mac_mads_mesh: one scale per axis, the granularity of disk i's x, y and r)
             const double sc = src.ltri ? src.delta : 1.0;
             double scx = sc, scy = sc, scr = sc;
-            if constexpr (kMesh) {
+            if constexpr (kMesh != 0) {
                 const double* const gm = src.mesh();
                 scx = gm[i];
                 scy = gm[N + i];
@@ -319,13 +336,29 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
                 cx[j] = plus ? xi + dx : xi - dx;
                 cy[j] = plus ? yi + dy : yi - dy;
                 cr[j] = plus ? ri + dr : ri - dr;
+                if constexpr (kMesh == kMeshKeys) {   // (int16 draws: exact in fp32)
+                    mx[j] = plus ? (float)dtab[kk] : -(float)dtab[kk];
+                    my[j] = plus ? (float)dtab[n + kk] : -(float)dtab[n + kk];
+                    mr[j] = plus ? (float)dtab[2 * n + kk] : -(float)dtab[2 * n + kk];
+                }
             }
             __syncthreads();   // the table is cleared next
         } else {
 #pragma unroll
             for (int j = 0; j < P; ++j) {
                 const int k = j < kIdxPer ? tid + j * kIdxThreads : (tid == 0 ? kIndexMaxK : K);
-                get3(min(k, K - 1), cx[j], cy[j], cr[j]);
+                if constexpr (kMesh == kMeshKeys) {
+                    const int kc = min(k, K - 1);
+                    double ex, ey, er;
+                    cx[j] = src.get_draw(kc, i, N, ex);
+                    cy[j] = src.get_draw(kc, N + i, N, ey);
+                    cr[j] = src.get_draw(kc, 2 * N + i, N, er);
+                    mx[j] = (float)ex;
+                    my[j] = (float)ey;
+                    mr[j] = (float)er;
+                } else {
+                    get3(min(k, K - 1), cx[j], cy[j], cr[j]);
+                }
             }
         }
         for (int q = tid; q < kIndexSlots; q += kIdxThreads) table[q] = -1;
@@ -336,6 +369,15 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
             const int k = j < kIdxPer ? tid + j * kIdxThreads : (tid == 0 ? kIndexMaxK : K);
             if (dead_cand(o.vp, k, K)) {
                 kx[k] = ky[k] = kr[k] = __builtin_bit_cast(float, kDeadKey);
+            } else if (kMesh == kMeshKeys && k < K) {
+                // the draws themselves, kept when fp32 holds them and the decode is the double
+                auto mk = [&](float m, double b, double g, double v) {
+                    ok &= __builtin_bit_cast(uint64_t, mesh_key_decode(b, g, (double)m)) == __builtin_bit_cast(uint64_t, v);
+                    return m;
+                };
+                kx[k] = mk(mx[j], bx, gx, cx[j]);
+                ky[k] = mk(my[j], by, gy, cy[j]);
+                kr[k] = mk(mr[j], br, gr, cr[j]);
             } else if (k < K) {
                 kx[k] = key_of(cx[j], bx, ok);
                 ky[k] = key_of(cy[j], by, ok);
@@ -471,6 +513,9 @@ __global__ __launch_bounds__(kIdxThreads) __attribute__((amdgpu_waves_per_eu(kPe
                 if (dead) {   // the failed candidates
                     d.cx = d.cy = d.r = 0.0;
                     d.T = -1.0;
+                } else if constexpr (kMesh == kMeshKeys) {
+                    d = make_disk(mesh_key_decode(bx, gx, (double)fx), mesh_key_decode(by, gy, (double)fy),
+                                  mesh_key_decode(br, gr, (double)fr));
                 } else {
                     d = make_disk(bx + (double)fx, by + (double)fy, br + (double)fr);
                 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "predicate.h"
+#include "mesh_key.h"
 #include "k_common.h"
 
 #pragma clang fp contract(off)
@@ -160,6 +161,9 @@ struct CandSrc {
     // (host only) the chain a generated poll takes under MAC_CHAIN_AUTO: 1 = the five-launch chain
     // (the host found the poll crowded: maxcover.hip host_crowded_disks), 0 = AUTO's history
     int route_five;
+    // (host only, in the struct's tail padding) a generated poll on a mesh keys its disks in mesh units
+    // (MAC_OPT_MESH_KEYS, mesh_key.h): the chains' kMesh == kMeshKeys builds
+    int mesh_keys;
     // Called at the top of every launch that reads the source: b = 2^ell from the device state;
     // false once the loop has stopped, or (launches after the prep: any_poll false) when the
     // prep rejected the poll whole (the launch returns at once). Uniform per workgroup.
@@ -206,9 +210,9 @@ struct CandSrc {
         }
     }
     // variable v's diagonal step at mesh step b = 2^ell (the whole-poll rejection, diag_rejects)
-    template <bool kMesh> __device__ __forceinline__ double diag_step(int v, double b) const
+    template <int kMesh> __device__ __forceinline__ double diag_step(int v, double b) const
     {
-        if constexpr (kMesh) return mesh_ptr()[v] * b;
+        if constexpr (kMesh != 0) return mesh_ptr()[v] * b;
         else return b;
     }
     // a full poll's value (np == 0), for the launches that select the poll kind at compile time
@@ -240,10 +244,25 @@ struct CandSrc {
     // The source selected at compile time (the fused chain's second and third launches, k_fiw.h):
     // kMat is a matrix source, read from cands alone — no generator code in that instantiation and
     // none of its operands held in registers — and never paused by a device state (no mst).
-    template <bool kMat, bool kMesh = false> __device__ __forceinline__ double val(int kl, int v, int N) const
+    template <bool kMat, int kMesh = 0> __device__ __forceinline__ double val(int kl, int v, int N) const
     {
         if constexpr (kMat) return cands[(int64_t)kl * ldc + v];
         else return cands ? cands[(int64_t)kl * ldc + v] : get_m<kMesh ? kOnMesh : kNoMesh>(kl, v, N);
+    }
+    // Mesh keys (mesh_key.h): a generated candidate's value as get_m<kOnMesh> builds it, and in e the
+    // signed draw behind it (+-entry, the integer the stream drew; 0.0 for a held variable)
+    __device__ __forceinline__ double get_draw(int kl, int v, int N, double& e) const
+    {
+        const int n = polled(N);
+        const int k = kl + k0;
+        const int kk = k < n ? k : k - n;
+        const bool held = v >= n;
+        const double xv = xinc[v];
+        const double en = entry(n, rp[held ? 0 : v], cp[kk]);
+        const double d = mesh_ptr()[held ? 0 : v] * en;
+        const double moved = k < n ? xv + d : xv - d;
+        e = held ? 0.0 : k < n ? en : -en;
+        return held ? xv : moved;
     }
     template <bool kMat> __device__ __forceinline__ bool resolve_as()
     {
@@ -251,6 +270,8 @@ struct CandSrc {
         else return resolve();
     }
 };
+
+static_assert(sizeof(CandSrc) == 120, "the launches' arguments keep their size");
 
 // ------------------------------------------------------------------ the prep launch
 // The first launch of every evaluation: workgroup cw takes candidates [8cw, 8cw + 8), thread u
@@ -354,7 +375,14 @@ constexpr int kPrepCX = 6;
 // the escape kKeyEsc (r field -512) and the value's three fp32 offsets go to the keysT rows
 // (k_index.h "Keys"). Either encoding satisfies v == v0 + (double)key, so equal keys still mean
 // equal disks; the index reads one word per candidate instead of three.
+// Mesh keys (kMesh == kMeshKeys: MAC_OPT_MESH_KEYS on a generated poll with a mesh; mesh_key.h): the
+// word holds the disk's signed draws (m_x, m_y, m_r) instead, base the incumbent and scale the disk's
+// granularities, built from the draws the launch has in hand before the product; a draw past its
+// field, or a decode that is not the double, leaves the escape word, marks the record inexact (the
+// identity map) and writes no fp32 row: mesh units and metres never meet in one key space.
 constexpr uint32_t kKeyEsc = 0x200u << 22;
+static_assert(kKeyEsc == kMeshKeyEsc, "one escape word");
+constexpr int kMeshKeys = 2;   // kMesh: 0 no mesh, 1 a mesh with value keys, 2 a mesh with mesh keys
 __device__ __forceinline__ bool key_int(double v, double b, double lim, int& d)
 {
     const double f = v - b;
@@ -437,7 +465,7 @@ struct PrepLds {
     double dred[kPrepU / kWave][4];   // per wave: its share of the displacement bound
 };
 
-template <bool kMat, int PC, bool kMesh = false>   // (kMesh: a generated poll on a mesh, CandSrc.step_m)
+template <bool kMat, int PC, int kMesh = 0>   // (kMesh: a generated poll on a mesh, CandSrc.step_m)
 __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned char* lds)
 {
     constexpr int kM = kMesh ? CandSrc::kOnMesh : CandSrc::kNoMesh;
@@ -479,6 +507,9 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
         const bool iv = u < nb;
         const int ii = min(i, N - 1);
         double v[NC][3];
+        // (mesh keys) per slot its word from the draws, and a bit when it does not pack or decode
+        [[maybe_unused]] uint32_t mkw[NC] = {};
+        [[maybe_unused]] uint32_t mkbad = 0u;
         if (!kMat && PC == 8 && a.pair) {
             // x +- B[v][col]: each draw once for the candidate pair (PC == 8: four columns)
 #pragma unroll
@@ -489,6 +520,21 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
                     const int vv = q * N + ii;
                     if (q == 2 && 2 * N >= np) {   // (uniform) an xy-only poll: the radius as it is, no draw
                         v[c][q] = v[c + 4][q] = a.src.xinc[vv];
+                        if constexpr (kMesh == kMeshKeys) {   // (held: m = 0)
+                            const double gq = a.src.mesh_ptr()[vv];
+                            mkbad |= (mesh_key_put(mkw[c], q, v[c][q], gq, 0.0, v[c][q]) ? 0u : 1u) << c;
+                            mkbad |= (mesh_key_put(mkw[c + 4], q, v[c][q], gq, 0.0, v[c][q]) ? 0u : 1u) << (c + 4);
+                        }
+                        continue;
+                    }
+                    if constexpr (kMesh == kMeshKeys) {
+                        const double xv = a.src.xinc[vv], gq = a.src.mesh_ptr()[vv];
+                        const double e = a.src.entry(np, a.src.rp[vv], a.src.cp[col]);
+                        const double d = gq * e;   // (step_m's product)
+                        v[c][q] = xv + d;
+                        v[c + 4][q] = xv - d;
+                        mkbad |= (mesh_key_put(mkw[c], q, xv, gq, e, v[c][q]) ? 0u : 1u) << c;
+                        mkbad |= (mesh_key_put(mkw[c + 4], q, xv, gq, -e, v[c + 4][q]) ? 0u : 1u) << (c + 4);
                         continue;
                     }
                     const double d = a.src.step_m<kM>(np, vv, a.src.rp[vv], a.src.cp[col]);
@@ -503,12 +549,32 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     if constexpr (kMat) v[c][q] = a.src.cands[(int64_t)k * a.src.ldc + q * N + ii];
-                    else v[c][q] = a.src.get_m<kM>(k, q * N + ii, N);
+                    else if constexpr (kMesh == kMeshKeys) {
+                        const int vv = q * N + ii;
+                        double e;
+                        v[c][q] = a.src.get_draw(k, vv, N, e);
+                        mkbad |= (mesh_key_put(mkw[c], q, a.src.xinc[vv], a.src.mesh_ptr()[vv], e, v[c][q]) ? 0u : 1u) << c;
+                    } else v[c][q] = a.src.get_m<kM>(k, q * N + ii, N);
+                }
+            }
+        }
+        if constexpr (kMesh == kMeshKeys) {
+            // the words leave at once (nothing here reads them back): only the escape bits stay live
+            // through the fold, for the record's flag
+            if (a.keysP && iv) {
+                uint32_t* const krow = a.keysP + (int64_t)i * a.ldk;
+#pragma unroll
+                for (int h = 0; h < PC / 4; ++h) {
+                    uint32_t w4[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) w4[e] = ((mkbad >> (4 * h + e)) & 1u) ? kKeyEsc : mkw[4 * h + e];
+                    *reinterpret_cast<uint4*>(krow + cand(4 * h)) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
                 }
             }
         }
         double base[3] = {0.0, 0.0, 0.0};   // candidate 0's values: the keys' base
-        if (a.keysP) {
+        // (mesh keys: the base of the fused chain's displacement bound alone)
+        if (a.keysP && (kMesh != kMeshKeys || a.pd)) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 if constexpr (kMat) base[q] = a.src.cands[q * N + ii];
@@ -676,7 +742,10 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
                 }
             }
             bool kb = false;   // a key of this disk is inexact (k_index.h "Keys")
-            if (a.keysP) {     // the keys: packed words (two 16-B stores), escapes in fp32
+            if constexpr (kMesh == kMeshKeys) {
+                // (the words were stored above; no fp32 row: a live escape is the identity map)
+                kb = a.keysP && (mkbad & ~dead) != 0u;
+            } else if (a.keysP) {     // the keys: packed words (two 16-B stores), escapes in fp32
                 uint32_t pk[NC];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
@@ -744,7 +813,7 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 // fold and the keys are exclusive branches, so the candidate values are dead on the folding
 // wave's path (80 VGPRs: two workgroups, 18 waves, fit a CU). Results are prep_block's bit for bit
 // (the same terms in the same order, the same keys and bound).
-template <bool kGen, bool kMesh = false>   // (kMesh: as prep_block's)
+template <bool kGen, int kMesh = 0>   // (kMesh: as prep_block's)
 __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned char* lds)
 {
     constexpr int kM = kMesh ? CandSrc::kOnMesh : CandSrc::kNoMesh;
@@ -779,6 +848,9 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     MAC_PREP_STAMP(0);
     double v[NC][3];
     double base[3] = {0.0, 0.0, 0.0};   // candidate 0's values: the keys' base
+    // (mesh keys) per slot its word from the draws, and a bit when it does not pack or decode
+    [[maybe_unused]] uint32_t mkw[NC] = {};
+    [[maybe_unused]] uint32_t mkbad = 0u;
     if (!fw) {
         if constexpr (kGen) {
 #pragma unroll
@@ -788,11 +860,30 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
                 const double xv = a.src.xinc[vv];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
+                    if constexpr (kMesh == kMeshKeys) {
+                        const double gq = a.src.mesh_ptr()[vv];
+                        const double e = a.src.entry(n3, rv, a.src.cp[3 * cw + c]);
+                        const double d = gq * e;   // (step_m's product)
+                        v[c][q] = xv + d;
+                        v[c + 3][q] = xv - d;
+                        mkbad |= (mesh_key_put(mkw[c], q, xv, gq, e, v[c][q]) ? 0u : 1u) << c;
+                        mkbad |= (mesh_key_put(mkw[c + 3], q, xv, gq, -e, v[c + 3][q]) ? 0u : 1u) << (c + 3);
+                        continue;
+                    }
                     const double d = a.src.step_m<kM>(n3, vv, rv, a.src.cp[3 * cw + c]);
                     v[c][q] = xv + d;
                     v[c + 3][q] = xv - d;
                 }
-                base[q] = xv + a.src.step_m<kM>(n3, vv, rv, a.src.cp[0]);
+                if (kMesh != kMeshKeys || a.pd)   // (mesh keys: the displacement bound's base alone)
+                    base[q] = xv + a.src.step_m<kM>(n3, vv, rv, a.src.cp[0]);
+            }
+            if constexpr (kMesh == kMeshKeys) {
+                // the words leave at once: only the escape bits stay live past the barrier
+                if (iv) {
+                    uint32_t* const krow = a.keysP + (int64_t)u * a.ldk;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) krow[cand(c)] = ((mkbad >> c) & 1u) ? kKeyEsc : mkw[c];
+                }
             }
         } else {
 #pragma unroll
@@ -925,10 +1016,17 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
         for (int c = 0; c < NC; ++c) {
             const double x = v[c][0], y = v[c][1], r = v[c][2];
             int dx = 0, dy = 0, dr = 0;
-            const bool packs = key_int(x, base[0], 1023.0, dx) && key_int(y, base[1], 1023.0, dy) &&
-                               key_int(r, base[2], 511.0, dr);
-            pk[c] = packs ? key_pack(dx, dy, dr) : kKeyEsc;
-            if (!packs && iv && cand(c) < K) {
+            bool packs;
+            if constexpr (kMesh == kMeshKeys) {   // (stored above; no fp32 row: an escape is the identity map)
+                packs = !((mkbad >> c) & 1u);
+                pk[c] = 0u;
+                kb |= !packs && !((dead >> c) & 1u);
+            } else {
+                packs = key_int(x, base[0], 1023.0, dx) && key_int(y, base[1], 1023.0, dy) &&
+                        key_int(r, base[2], 511.0, dr);
+                pk[c] = packs ? key_pack(dx, dy, dr) : kKeyEsc;
+            }
+            if (kMesh != kMeshKeys && !packs && iv && cand(c) < K) {
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     const float f = (float)(v[c][q] - base[q]);
@@ -952,7 +1050,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
                 dml = fmax(dml, el);
             }
         }
-        if (iv) {
+        if (kMesh != kMeshKeys && iv) {
             uint32_t* const krow = a.keysP + (int64_t)u * a.ldk;
             if constexpr (kGen) {   // two runs of three words (plus and minus candidates)
 #pragma unroll
@@ -1027,7 +1125,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     }
 }
 
-template <int PC, bool kX = false, bool kGen = false, bool kMesh = false>
+template <int PC, bool kX = false, bool kGen = false, int kMesh = 0>
 __device__ __forceinline__ void prep_body(uint64_t* ts, PrepArgs& a)
 {
     ts_begin(ts);   // profiling only (the chain's first launch: k_common.h)
@@ -1053,7 +1151,7 @@ __device__ __forceinline__ void prep_body(uint64_t* ts, PrepArgs& a)
 
 // kPrepC candidates per workgroup, two workgroups per CU
 // kMesh: a generated poll on a mesh (mac_mads_mesh), its own build: without a mesh the code it was
-template <bool kMesh = false>
+template <int kMesh = 0>
 __global__ __launch_bounds__(kPrepU) __attribute__((amdgpu_waves_per_eu(4))) void prep_kernel(uint64_t* ts, PrepArgs a)
 {
     prep_body<kPrepC, false, false, kMesh>(ts, a);
@@ -1065,7 +1163,7 @@ __global__ __launch_bounds__(kPrepU) __attribute__((amdgpu_waves_per_eu(4))) voi
 // matrix path spill-free, where one kernel holding both paths spilled 13 VGPRs: config 4's prep
 // 20.7 -> 26.1 us). 6 waves per EU beat 5 for the generated path too (prep 17.9 vs 23.7 us with
 // 82 VGPRs and no spill: the two it spills here are off the hot path)
-template <bool kGen, bool kMesh = false>   // (kMesh: as prep_kernel's; generated polls only)
+template <bool kGen, int kMesh = 0>   // (kMesh: as prep_kernel's; generated polls only)
 __global__ __launch_bounds__(kPrepU + kWave) __attribute__((amdgpu_waves_per_eu(6))) void prep_x_kernel(uint64_t* ts, PrepArgs a)
 {
     static_assert(kGen || !kMesh, "a mesh belongs to a generated poll");

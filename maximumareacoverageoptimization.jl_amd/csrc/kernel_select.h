@@ -48,23 +48,26 @@ static uint32_t mask_lds(int S) { return (uint32_t)(17 * kConsBlock * S); }
 
 // (a mesh belongs to a generated poll: prep_x_kernel's matrix build has none)
 using PrepKern = void (*)(uint64_t*, PrepArgs);
-static PrepKern prep_kern(int kind, bool mesh)
+// (mesh: EvalPlan.mesh, the kMesh argument: 0 none, 1 a mesh with value keys, kMeshKeys)
+static PrepKern prep_kern(int kind, int mesh)
 {
-    if (kind == kPrepXGen) return mesh ? prep_x_kernel<true, true> : prep_x_kernel<true>;
+    if (kind == kPrepXGen)
+        return mesh == kMeshKeys ? prep_x_kernel<true, kMeshKeys> : mesh ? prep_x_kernel<true, 1> : prep_x_kernel<true>;
     if (kind == kPrepXMatrix) return prep_x_kernel<false>;
-    return mesh ? prep_kernel<true> : prep_kernel<false>;
+    return mesh == kMeshKeys ? prep_kernel<kMeshKeys> : mesh ? prep_kernel<1> : prep_kernel<0>;
 }
 static dim3 prep_block(int kind) { return dim3(kind == kPrepChains ? kPrepU : kPrepU + kWave); }
 
 // (an xy-only poll's and a mesh's kernels are their own instantiations: the full poll's stay as they were)
 using IdxKern = void (*)(uint64_t*, CandSrc, int, int, Grid, int, IndexOut);
 template <bool kKeys, int kPer>
-static IdxKern index_kern_of(bool xy, bool mesh)
+static IdxKern index_kern_of(bool xy, int mesh)
 {
-    return mesh ? (xy ? disk_index_kernel<kKeys, kPer, true, true> : disk_index_kernel<kKeys, kPer, false, true>)
+    return mesh == kMeshKeys ? (xy ? disk_index_kernel<kKeys, kPer, true, kMeshKeys> : disk_index_kernel<kKeys, kPer, false, kMeshKeys>)
+         : mesh ? (xy ? disk_index_kernel<kKeys, kPer, true, 1> : disk_index_kernel<kKeys, kPer, false, 1>)
                 : (xy ? disk_index_kernel<kKeys, kPer, true> : disk_index_kernel<kKeys, kPer>);
 }
-static IdxKern index_kern(bool keys, bool wide, bool xy, bool mesh)
+static IdxKern index_kern(bool keys, bool wide, bool xy, int mesh)
 {
     return keys ? (wide ? index_kern_of<true, kIdxPerWide>(xy, mesh) : index_kern_of<true, kIdxPer>(xy, mesh))
                 : (wide ? index_kern_of<false, kIdxPerWide>(xy, mesh) : index_kern_of<false, kIdxPer>(xy, mesh));
@@ -74,11 +77,13 @@ static IdxKern index_kern(bool keys, bool wide, bool xy, bool mesh)
 // has no generator code in it; generated and basis-form polls take the other (kXY, kMesh: theirs only)
 using FiwKern = void (*)(uint64_t*, FwArgs);
 template <bool kCounts>
-static FiwKern fiw_kern_of(bool mat, bool mesh)
+static FiwKern fiw_kern_of(bool mat, int mesh)
 {
-    return mat ? fiw_kernel<kCounts, true> : mesh ? fiw_kernel<kCounts, false, true> : fiw_kernel<kCounts, false>;
+    return mat ? fiw_kernel<kCounts, true>
+         : mesh == kMeshKeys ? fiw_kernel<kCounts, false, kMeshKeys>
+         : mesh ? fiw_kernel<kCounts, false, 1> : fiw_kernel<kCounts, false>;
 }
-static FiwKern fiw_kern(bool counts, bool mat, bool mesh)
+static FiwKern fiw_kern(bool counts, bool mat, int mesh)
 {
     return counts ? fiw_kern_of<true>(mat, mesh) : fiw_kern_of<false>(mat, mesh);
 }
@@ -86,13 +91,14 @@ static FiwKern fiw_kern(bool counts, bool mat, bool mesh)
 using Fin2Kern = void (*)(const unsigned*, const double*, int, int, int, double, const double*, double*, double*,
                           FinBest, F2Shared, uint64_t*);
 template <bool kCounts>
-static Fin2Kern fin2_kern_of(bool mat, bool xy, bool mesh)
+static Fin2Kern fin2_kern_of(bool mat, bool xy, int mesh)
 {
     return mat ? fin2_kernel<kCounts, true>
-         : mesh ? (xy ? fin2_kernel<kCounts, false, true, true> : fin2_kernel<kCounts, false, false, true>)
+         : mesh == kMeshKeys ? (xy ? fin2_kernel<kCounts, false, true, kMeshKeys> : fin2_kernel<kCounts, false, false, kMeshKeys>)
+         : mesh ? (xy ? fin2_kernel<kCounts, false, true, 1> : fin2_kernel<kCounts, false, false, 1>)
          : xy ? fin2_kernel<kCounts, false, true> : fin2_kernel<kCounts, false>;
 }
-static Fin2Kern fin2_kern(bool counts, bool mat, bool xy, bool mesh)
+static Fin2Kern fin2_kern(bool counts, bool mat, bool xy, int mesh)
 {
     return counts ? fin2_kern_of<true>(mat, xy, mesh) : fin2_kern_of<false>(mat, xy, mesh);
 }

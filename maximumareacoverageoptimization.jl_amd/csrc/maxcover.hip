@@ -273,6 +273,7 @@ struct mac_ctx {
     int algo = MAC_ALGO_AUTO;
     int shared_mode = MAC_SHARED_AUTO;   // MAC_OPT_SHARED
     int chain = MAC_CHAIN_AUTO;          // MAC_OPT_CHAIN
+    int mesh_keys = MAC_KEYS_VALUE;      // MAC_OPT_MESH_KEYS (read when a MADS run or stepper begins)
     bool profile = false;
     // In-kernel launch timing (k_common.h ts_begin / ts_end): each profiled walk launch takes
     // nwg consecutive {start, end} slots of `stamps`. a: the scan / tiled launch, b: the poll
@@ -1218,7 +1219,7 @@ static void enqueue_finalize(EvalRun& r, const WalkOut& w)
     uint64_t* tsf = r.ts_chain(kRoleFin, pl.nfin);
     // (fb.np: the pipelined loop's update of an xy-only poll)
     // (... and on a mesh: the builds with the scaled update; a stepper's finalize applies none)
-    hipLaunchKernelGGL(finalize_kern(fb.np != 0, pl.mesh && fb.st != nullptr), dim3(pl.nfin), dim3(kFinThreads), 0,
+    hipLaunchKernelGGL(finalize_kern(fb.np != 0, pl.mesh != 0 && fb.st != nullptr), dim3(pl.nfin), dim3(kFinThreads), 0,
                        r.s, r.L->partial.as<double>(), r.d_mode, rq.N, w.n_other, rq.K, rq.N, w.d_umap, w.d_spart,
                        w.d_ncount, pl.counts, r.ctx->w0, r.d_vp, rq.d_area, rq.d_obj, fb, tsf);
     HCK(hipGetLastError());
@@ -1240,6 +1241,7 @@ static RouteIn route_in(const mac_ctx* ctx, const EvalReq& rq, bool mask)
     in.mesh = src.mesh() != nullptr;
     in.mst = src.mst != nullptr;
     in.route_five = src.route_five != 0;
+    in.mesh_keys = src.mesh_keys != 0;
     in.b = src.b;
     in.delta = src.delta;
     in.want_area = rq.d_area != nullptr;
@@ -1809,9 +1811,8 @@ int32_t mac_diag_tiles(double c, double r, double g0, double invS, int32_t n, in
 // out = {poll_possible, walk_forced, iper, want_keys, pair, gen_x, mesh, nchain, G, units,
 // fused_eligible, excl, counts, prep_fused (PrepKind), nprep, xbase, prep_five_runs, prep_five, nrec,
 // nfw, nidx, nfin2, nfin}
-int32_t mac_diag_route(const int64_t* in, double delta, int64_t* out, int32_t n_out)
+static RouteIn diag_route_in(const int64_t* in, double delta)
 {
-    if (!in || !out || n_out < 0 || in[17] < 0 || in[18] < 1) return MAC_E_INVAL;
     RouteIn ri;
     ri.algo = (int)in[0];
     ri.chain = (int)in[1];
@@ -1833,11 +1834,80 @@ int32_t mac_diag_route(const int64_t* in, double delta, int64_t* out, int32_t n_
     ri.tiled = in[16] != 0;
     ri.N = (int)in[17];
     ri.K = (int)in[18];
+    return ri;
+}
+
+static int32_t diag_route_out(const RouteIn& ri, int64_t* out, int32_t n_out)
+{
     const EvalPlan p = eval_plan(ri);
     const int64_t v[] = {p.poll_possible, p.walk_forced, p.iper, p.want_keys, p.pair, p.gen_x, p.mesh, p.nchain,
                          p.G, p.units, p.fused_eligible, p.excl, p.counts, p.prep_fused, p.nprep, p.xbase,
                          p.prep_five_runs, p.prep_five, p.nrec, p.nfw, p.nidx, p.nfin2, p.nfin};
     for (int q = 0; q < n_out && q < (int)(sizeof v / sizeof v[0]); ++q) out[q] = v[q];
+    return MAC_OK;
+}
+
+int32_t mac_diag_route(const int64_t* in, double delta, int64_t* out, int32_t n_out)
+{
+    if (!in || !out || n_out < 0 || in[17] < 0 || in[18] < 1) return MAC_E_INVAL;
+    return diag_route_out(diag_route_in(in, delta), out, n_out);
+}
+
+// The chain word of a run on the mesh g (its n_p polled entries; null: none) whose layout the host found
+// crowded or not: a non-integer granularity sends value keys to the five-launch chain (mac_mads_begin*);
+// mesh keys (MAC_OPT_MESH_KEYS) pack at every granularity and follow the crowding estimate alone.
+static int mads_route_five(bool crowded, const double* g, int np, bool mesh_keys)
+{
+    int five = crowded ? 1 : 0;
+    for (int v = 0; v < np && g && !mesh_keys; ++v)
+        if (g[v] != std::floor(g[v])) five = 1;
+    return five;
+}
+
+// host only, every build (not declared in maxcover.h): mac_diag_route with the key mode. `in` as above
+// (its route_five word is ignored) with in[19] = MAC_OPT_MESH_KEYS's value appended; g: the n_g polled
+// granularities of a run's mesh (n_g = 0: no mesh) and `crowded` its begin's crowding verdict, from which
+// the run's chain word follows as in mac_mads_begin* (mads_route_five; returned in *route_five). out's
+// mesh word is the kMesh argument of the chains' builds: 0 none, 1 value keys, 2 mesh keys.
+int32_t mac_diag_route_keys(const int64_t* in, double delta, int64_t* out, int32_t n_out, const double* g,
+                            int32_t n_g, int32_t crowded, int32_t* route_five)
+{
+    if (!in || !out || n_out < 0 || in[17] < 0 || in[18] < 1 || n_g < 0 || (n_g && !g)) return MAC_E_INVAL;
+    if (in[19] != MAC_KEYS_VALUE && in[19] != MAC_KEYS_MESH) return MAC_E_INVAL;
+    RouteIn ri = diag_route_in(in, delta);
+    ri.mesh = n_g > 0;
+    ri.mesh_keys = in[19] == MAC_KEYS_MESH && n_g > 0;
+    ri.route_five = mads_route_five(crowded != 0, n_g ? g : nullptr, n_g, ri.mesh_keys) != 0;
+    if (route_five) *route_five = ri.route_five ? 1 : 0;
+    return diag_route_out(ri, out, n_out);
+}
+
+// host only, every build (not declared in maxcover.h): mesh_key.h as the kernels inline it, over n
+// triples: x, g, v = [n][3] doubles (the incumbent's disk, its granularities, the candidate's doubles;
+// v null: the decode itself), m = [n][3] signed draws. word[n]: the packed word, or the escape when a
+// draw is past its field or a decode is not v bit for bit; dec[n][3]: the decodes; flags[n]: bit 0 the
+// draws pack, bit 1 every decode reproduces v.
+int32_t mac_diag_mesh_key(int64_t n, const double* x, const double* g, const int32_t* m, const double* v,
+                          uint32_t* word, double* dec, int32_t* flags)
+{
+    if (n < 0 || !x || !g || !m || !word || !dec || !flags) return MAC_E_INVAL;
+    for (int64_t t = 0; t < n; ++t) {
+        // (the kernels build a word a field at a time, mesh_key_put: the draw's range and the decode's
+        // bits in one; mesh_key_pack is the same word from the three integers)
+        uint32_t w = 0u, wp = 0u;
+        bool put = true, exact = true;
+        for (int q = 0; q < 3; ++q) {
+            const int64_t at = 3 * t + q;
+            dec[at] = mesh_key_decode(x[at], g[at], (double)m[at]);
+            const double want = v ? v[at] : dec[at];
+            exact = mesh_key_exact(x[at], g[at], m[at], want) && exact;
+            put = mesh_key_put(w, q, x[at], g[at], (double)m[at], want) && put;
+        }
+        const bool packed = mesh_key_pack(m[3 * t], m[3 * t + 1], m[3 * t + 2], wp);
+        if (put != (packed && exact) || (put && w != wp)) return MAC_E_INVAL;   // (never: one encoding)
+        word[t] = put ? w : kMeshKeyEsc;
+        flags[t] = (packed ? 1 : 0) | (exact ? 2 : 0);
+    }
     return MAC_OK;
 }
 
@@ -2174,6 +2244,10 @@ int32_t mac_set_option(mac_ctx* ctx, int32_t option, int64_t value)
     case MAC_OPT_CHAIN:
         if (value < MAC_CHAIN_AUTO || value > MAC_CHAIN_FUSED) return fail(MAC_E_INVAL, "bad chain");
         ctx->chain = (int)value;
+        return MAC_OK;
+    case MAC_OPT_MESH_KEYS:
+        if (value != MAC_KEYS_VALUE && value != MAC_KEYS_MESH) return fail(MAC_E_INVAL, "bad mesh keys mode");
+        ctx->mesh_keys = (int)value;
         return MAC_OK;
     case MAC_OPT_TILE_POINTS:
         if (value < 1 || value > 4096) return fail(MAC_E_INVAL, "tile points out of range");
@@ -2718,6 +2792,7 @@ struct mac_mads {
     bool slotted = false;
     int64_t slot_fallbacks = 0;   // slot waits that timed out (copy + sync instead)
     int route_five = 0;           // the polls are crowded (host_crowded_disks at begin): five-launch chain
+    int mesh_keys = 0;            // the run keys its polls in mesh units (MAC_OPT_MESH_KEYS as it began, on a mesh)
     double* ext_best = nullptr;   // mac_mads_best_buffer: the polls' best goes here
     // the mesh (mac_mads_begin_mesh): the granularity of every variable, host copy and device copy
     // (empty / null: 1.0 everywhere, the calls without a mesh)
@@ -3062,8 +3137,10 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
         // (tools/mads_granularity_time.py, profiles/mads_granularity.json): 14.6 ms per MPC step
         // through the five-launch chain against 73.9 ms through the fused one. (The polled variables'
         // entries: an xy-only poll never steps by g_r.)
-        for (int v = 0; v < np && !m->g.empty(); ++v)
-            if (m->g[v] != std::floor(m->g[v])) m->route_five = 1;
+        // With mesh keys (MAC_OPT_MESH_KEYS; mesh_key.h) every granularity packs as the unit mesh does, and
+        // AUTO follows the crowding estimate alone. The run keeps the mode it begins with.
+        m->mesh_keys = ctx->mesh_keys == MAC_KEYS_MESH && !m->g.empty() ? 1 : 0;
+        m->route_five = mads_route_five(m->route_five != 0, m->g.empty() ? nullptr : m->g.data(), np, m->mesh_keys != 0);
         m->state = prm->seed;
         m->T = (uint64_t)np * (uint64_t)(np - 1) / 2;
         m->per_iter = (uint64_t)np + m->T + 2 * (uint64_t)np;   // ltmads_basis(n_p)'s draws
@@ -3130,6 +3207,7 @@ int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* bes
         src.k0 = (int)m->lo;
         src.route_five = m->route_five;
         src.set_mesh(m->d_g);
+        src.mesh_keys = m->mesh_keys;
         mads_best_of(m, src, Kc, m->lo, true);
     }
     const auto tb = clk::now();
@@ -3237,6 +3315,7 @@ int32_t mac_mads_poll_ahead(mac_mads* m, int32_t ahead, int32_t* done, double* b
     src.k0 = (int)m->lo;
     src.route_five = m->route_five;
     src.set_mesh(m->d_g);
+        src.mesh_keys = m->mesh_keys;
     mads_best_of(m, src, Kc, m->lo, true);
     uint64_t fe = 0;
     mads_wait_best(m, best_obj, best_idx, &fe);
@@ -3432,6 +3511,7 @@ static void mads_run_pipelined(mac_mads* m)
         src.mst = dst;
         src.route_five = m->route_five;
         src.set_mesh(m->d_g);
+        src.mesh_keys = m->mesh_keys;
         FinBest fbm{};
         fbm.st = dst;
         fbm.x = src.xinc;
@@ -4892,6 +4972,7 @@ static void mads_run_prog_loop(mac_mads* m, const mac_prog* prog, double h0, dou
             src.k0 = 0;
             src.route_five = m->route_five;
             src.set_mesh(m->d_g);
+        src.mesh_keys = m->mesh_keys;
             ProgLaunch pl{pargs, h_max, d_h[c]};
             if (m->xy) {   // the radii are held: every candidate's h is the centre's (<= h_max)
                 double* hh = reinterpret_cast<double*>(hs + ((stage_c + 7) & ~(size_t)7));

@@ -43,13 +43,47 @@ def verdict(a, b):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ab", required=True)
+    ap.add_argument("--ab", default=None, help="(optional) tools/ab.sh's logs")
+    ap.add_argument("--plain5", default=None, help="(optional) A<r>.log / B<r>.log of plain `bench.py --config 5` runs")
+    ap.add_argument("--dumps", nargs=2, default=None, metavar=("A_DIR", "B_DIR"),
+                    help="(optional) bench.py --dump-outputs directories of the two builds: compared byte for byte")
     ap.add_argument("--plain", required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--note", default="")
     a = ap.parse_args()
-    ab = {v: runs(a.ab, v) for v in "AB"}
     pl = {v: runs(a.plain, v) for v in "AB"}
+    if not a.ab:   # plain runs alone (and config 5's, and the dumped outputs)
+        out = {"note": a.note,
+               "method": "plain `python bench.py` runs of both builds on one box, alternating, the order swapped "
+                         "each round; A = the parent's libmaxcover.so, B = this change's",
+               "plain_runs": pl,
+               "plain_ms_per_step": verdict([r["ms_per_step"] for r in pl["A"]], [r["ms_per_step"] for r in pl["B"]])}
+        keys = ["plain_ms_per_step"]
+        if a.plain5:
+            p5 = {v: runs(a.plain5, v) for v in "AB"}
+            out["config5_runs"] = p5
+            out["config5_ms_per_step"] = verdict([r["ms_per_step"] for r in p5["A"]], [r["ms_per_step"] for r in p5["B"]])
+            keys.append("config5_ms_per_step")
+        for k in keys:   # B inside A's own spread: no cost
+            v = out[k]
+            v["B_median_inside_A_spread"] = min(v["A"]) <= v["B_median"] <= max(v["A"])
+        if a.dumps:
+            names = sorted(os.path.relpath(p, a.dumps[0]) for p in glob.glob(os.path.join(a.dumps[0], "**", "*"), recursive=True)
+                           if os.path.isfile(p))
+            same = []
+            for n in names:
+                pb = os.path.join(a.dumps[1], n)
+                with open(os.path.join(a.dumps[0], n), "rb") as fa:
+                    da = fa.read()
+                same.append(os.path.isfile(pb) and open(pb, "rb").read() == da)
+            out["dumped_outputs"] = {"files": names, "identical": bool(names) and all(same)}
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+        for k in keys:
+            print(k, {q: out[k][q] for q in ("A_median", "B_median", "A_range", "B_range", "B_median_inside_A_spread")})
+        print("dumped_outputs", out.get("dumped_outputs"))
+        return
+    ab = {v: runs(a.ab, v) for v in "AB"}
     out = {"note": a.note,
            "method": "tools/ab.sh A.so B.so 4 (alternating runs on one box, bench.py --full --no-cpu "
                      "--no-extras --steps 40), then plain `python bench.py` three times per build, "
