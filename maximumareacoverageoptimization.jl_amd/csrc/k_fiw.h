@@ -298,8 +298,10 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
     constexpr int P = kFwPer + 1;
     auto kof = [&](int j) { return j < kFwPer ? tid * kFwPer + j : (tid == 0 ? kFwMaxK : K); };
 
-    // ---- one round trip: this disk's key row and failure bytes (16-B and 4-B vector loads),
-    // candidate 0's disk i, the displacement partials, the lower disks' bases (first two batches)
+    // ---- one round trip: this disk's key row and failure bytes (16-B and 4-B vector loads; thread
+    // 0's extra word and byte at K > kFwMaxK among them), candidate 0's disk i, the displacement
+    // partials, the lower disks' bases (first two batches). Every load is issued, straight-line and
+    // at an always-valid address, before anything that was loaded is looked at (the asm below).
     int4 RG = make_int4(0, -1, 0, -1);
     bool ident;
     int rf0 = 0, rf1 = 0;   // the first row batch's runs (thread tid: row RG.z + tid), kept in flight
@@ -313,40 +315,80 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
     {
         const uint32_t* krow = src.keysP + (int64_t)i * src.ldk;
         uint32_t pq[P];
+        typedef uint32_t V4u __attribute__((ext_vector_type(4)));
+        V4u q4[kFwPer / 4];
+        uint32_t dw[kFwPer / 4];
         bool dj[P];
+        // (the key row and the failure words first: their consumer then needs only a counted wait.
+        // No branch here either: a thread past the row's end reads the row's last four words, and
+        // without failure bytes the key row's own bytes; both are dropped by value below)
+        const uint8_t* const drow = a.dead ? a.dead : reinterpret_cast<const uint8_t*>(krow);
 #pragma unroll
         for (int c = 0; c < kFwPer / 4; ++c) {
-            const int b0 = tid * kFwPer + 4 * c;   // (b0 % 4 == 0 and ldk % 32 == 0: b0 < ldk => b0 + 4 <= ldk)
-            const uint4 q4 = b0 < src.ldk ? *reinterpret_cast<const uint4*>(krow + b0) : make_uint4(0, 0, 0, 0);
-            const uint32_t d4 = a.dead && b0 < src.ldk ? *reinterpret_cast<const uint32_t*>(a.dead + b0) : 0u;
-            pq[4 * c] = q4.x;
-            pq[4 * c + 1] = q4.y;
-            pq[4 * c + 2] = q4.z;
-            pq[4 * c + 3] = q4.w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dj[4 * c + e] = ((d4 >> (8 * e)) & 0xFFu) != 0 && b0 + e < K;
+            // (b0 % 4 == 0 and ldk % 32 == 0: b0 < ldk => b0 + 4 <= ldk; the dead bytes are >= ldk)
+            const int b0c = min(tid * kFwPer + 4 * c, src.ldk - 4);
+            q4[c] = *reinterpret_cast<const V4u*>(krow + b0c);
+            dw[c] = *reinterpret_cast<const uint32_t*>(drow + b0c);
         }
-        pq[kFwPer] = tid == 0 && K > kFwMaxK ? krow[kFwMaxK] : 0u;
-        dj[kFwPer] = tid == 0 && K > kFwMaxK && a.dead && a.dead[kFwMaxK] != 0;
+        // candidate kFwMaxK's word and failure byte (thread 0 alone uses them), loaded by every thread
+        // without a branch: word 0 of the row when K <= kFwMaxK, a byte of the key row without failure
+        // bytes, neither one looked at then. (A branch here made wave 0 wait for its key row before
+        // it issued the rest of the round trip.)
+        const bool xk = K > kFwMaxK;
+        uint32_t xw = krow[xk ? kFwMaxK : 0];
+        uint32_t xb = *(a.dead ? a.dead + (xk ? kFwMaxK : 0) : reinterpret_cast<const uint8_t*>(krow));
         const double bx = src_val<kMat, kMesh>(src, 0, i, N), by = src_val<kMat, kMesh>(src, 0, N + i, N),
                      br = src_val<kMat, kMesh>(src, 0, 2 * N + i, N);
-        double dmx = -__builtin_inf(), dmy = -__builtin_inf(), dmr = -__builtin_inf(), dml = -__builtin_inf();
-        for (int q = tid; q < a.npd; q += kFwThreads) {
-            const double4 d4 = a.pd[q];
-            dmx = fmax(dmx, d4.x);
-            dmy = fmax(dmy, d4.y);
-            dmr = fmax(dmr, d4.z);
-            dml = fmax(dml, d4.w);
-        }
+        // the displacement partials: two records a thread, clamped addresses, left out by value.
+        // npd <= 512 = 2 kFwThreads on every fused route (eval_plan.h nprep: K / kPrepCX <= 512
+        // workgroups of a matrix prep, ceil(K / kPrepC) <= 385 chains, N <= kPrepU = 512 of a
+        // generated poll), so the loop below cannot run today; it keeps a larger launch correct.
+        const int plast = max(a.npd, 1) - 1;
+        const double4 pd0 = a.pd[min(tid, plast)], pd1 = a.pd[min(tid + kFwThreads, plast)];
+        // the lower disks' bases. A matrix source reads them at clamped addresses (rows of lower
+        // disks only) and drops them by value; a generated source computes them, so only j < i do.
         double jb[2][3];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int j = tid + q * kFwThreads;
-            const int jc = min(j, N - 1);
-            jb[q][0] = j < i ? src_val<kMat, kMesh>(src, 0, jc, N) : 0.0;
-            jb[q][1] = j < i ? src_val<kMat, kMesh>(src, 0, N + jc, N) : 0.0;
-            jb[q][2] = j < i ? src_val<kMat, kMesh>(src, 0, 2 * N + jc, N) : 0.0;
+            if constexpr (kMat) {
+                const int jc = min(j, max(i - 1, 0));
+                jb[q][0] = src_val<kMat, kMesh>(src, 0, jc, N);
+                jb[q][1] = src_val<kMat, kMesh>(src, 0, N + jc, N);
+                jb[q][2] = src_val<kMat, kMesh>(src, 0, 2 * N + jc, N);
+            } else {
+                const int jc = min(j, N - 1);
+                jb[q][0] = j < i ? src_val<kMat, kMesh>(src, 0, jc, N) : 0.0;
+                jb[q][1] = j < i ? src_val<kMat, kMesh>(src, 0, N + jc, N) : 0.0;
+                jb[q][2] = j < i ? src_val<kMat, kMesh>(src, 0, 2 * N + jc, N) : 0.0;
+            }
         }
+        // The empty asm keeps every use of a key or failure word below the issue of the loads above;
+        // the language does not promise that order, so after a compiler change check the ISA (make
+        // asm, or hipcc -S --offload-device-only) of every instantiation. In the matrix builds the
+        // three key loads (dwordx4), the three failure words, the extra word and byte, candidate
+        // 0's three values, four dwordx4 of partials and six dwordx2 of bases stand back to back
+        // with no branch and no s_waitcnt vmcnt between them; the first wait after them is counted
+        // (the partials and the bases stay in flight) and no vmcnt(0) stands before the shuffles.
+        static_assert(kFwPer == 12, "the asm below names the three key loads");
+        asm volatile(""
+                     : "+v"(q4[0]), "+v"(q4[1]), "+v"(q4[2]), "+v"(dw[0]), "+v"(dw[1]), "+v"(dw[2]), "+v"(xw),
+                       "+v"(xb)
+                     :
+                     : "memory");
+#pragma unroll
+        for (int c = 0; c < kFwPer / 4; ++c) {
+            const int b0 = tid * kFwPer + 4 * c;
+            const bool in = b0 < src.ldk;
+            const uint32_t d4 = a.dead && in ? dw[c] : 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                pq[4 * c + e] = in ? q4[c][e] : 0u;
+                dj[4 * c + e] = ((d4 >> (8 * e)) & 0xFFu) != 0 && b0 + e < K;
+            }
+        }
+        pq[kFwPer] = tid == 0 && xk ? xw : 0u;
+        dj[kFwPer] = tid == 0 && xk && a.dead && xb != 0;
         if (tid == 0) {
             ucnt = 0;
             ncnt = 0;
@@ -373,6 +415,22 @@ __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(2)))
             }
             own_store(kx, kw, tid, K);
             own_store(zbuf, zw, tid, K);
+        }
+        // the partials, first looked at here (the same fmax chain, in record order, as a loop's)
+        double dmx = -__builtin_inf(), dmy = -__builtin_inf(), dmr = -__builtin_inf(), dml = -__builtin_inf();
+        {
+            const bool h0 = tid < a.npd, h1 = tid + kFwThreads < a.npd;
+            dmx = fmax(fmax(dmx, h0 ? pd0.x : -__builtin_inf()), h1 ? pd1.x : -__builtin_inf());
+            dmy = fmax(fmax(dmy, h0 ? pd0.y : -__builtin_inf()), h1 ? pd1.y : -__builtin_inf());
+            dmr = fmax(fmax(dmr, h0 ? pd0.z : -__builtin_inf()), h1 ? pd1.z : -__builtin_inf());
+            dml = fmax(fmax(dml, h0 ? pd0.w : -__builtin_inf()), h1 ? pd1.w : -__builtin_inf());
+        }
+        for (int q = tid + 2 * kFwThreads; q < a.npd; q += kFwThreads) {
+            const double4 d4 = a.pd[q];
+            dmx = fmax(dmx, d4.x);
+            dmy = fmax(dmy, d4.y);
+            dmr = fmax(dmr, d4.z);
+            dml = fmax(dml, d4.w);
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {

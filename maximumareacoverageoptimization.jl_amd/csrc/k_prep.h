@@ -852,6 +852,30 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     [[maybe_unused]] uint32_t mkw[NC] = {};
     [[maybe_unused]] uint32_t mkbad = 0u;
     if (!fw) {
+        // The penalty's own inputs (prev, rmax, the cons3 threshold or the raw d_lim: N-sized) are
+        // issued ahead of the matrix loads and first looked at behind them (the asm below), so z1
+        // and the threshold are worked out while the candidates' values are in flight.
+        // (Every per-UAV load below is a uniform base plus one of three 32-bit byte offsets, UAV ii's
+        // x, y and r: a scalar base and a shared offset register a load, not a 64-bit address each.)
+        [[maybe_unused]] const uint32_t ob[3] = {(uint32_t)ii * 8u, (uint32_t)(N + ii) * 8u,
+                                                 (uint32_t)(2 * N + ii) * 8u};
+        [[maybe_unused]] auto at = [](const double* p, uint32_t o) {
+            return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(p) + o);
+        };
+        // (A generated poll issues the five together behind its draws instead, without the pins:
+        // held across the generator's 64-bit arithmetic they cost every kGen build spills.)
+        double p1x = 0.0, p1y = 0.0, p1r = 0.0, rm = 0.0, dl = 0.0;
+        if constexpr (!kGen) {
+            if (obj) {
+                if (pa.prev) {
+                    p1x = at(pa.prev, ob[0]);
+                    p1y = at(pa.prev, ob[1]);
+                    p1r = at(pa.prev, ob[2]);
+                    dl = at(pa.dlimT ? pa.dlimT : pa.dlim, ob[0]);
+                }
+                if (pa.rmax) rm = at(pa.rmax, ob[0]);
+            }
+        }
         if constexpr (kGen) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
@@ -889,18 +913,37 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
                 const int k = min(cand(c), K - 1);
+                const double* const col = a.src.cands + (int64_t)k * a.src.ldc;   // (uniform)
 #pragma unroll
-                for (int q = 0; q < 3; ++q) v[c][q] = a.src.cands[(int64_t)k * a.src.ldc + q * N + ii];
+                for (int q = 0; q < 3; ++q) v[c][q] = at(col, ob[q]);
             }
 #pragma unroll
-            for (int q = 0; q < 3; ++q) base[q] = a.src.cands[q * N + ii];
+            for (int q = 0; q < 3; ++q) base[q] = at(a.src.cands, ob[q]);
         }
         if (obj) {
+            if constexpr (kGen) {
+                if (pa.prev) {
+                    p1x = pa.prev[ii];
+                    p1y = pa.prev[N + ii];
+                    p1r = pa.prev[2 * N + ii];
+                    dl = pa.dlimT ? pa.dlimT[ii] : pa.dlim[ii];
+                }
+                if (pa.rmax) rm = pa.rmax[ii];
+            }
+            // The first empty asm keeps every use of the five small values below the issue of the
+            // candidates' loads; the second keeps z1 and the threshold above the first use of a
+            // candidate's value. The language promises neither order, so after a compiler change check
+            // the ISA (make asm, or hipcc -S --offload-device-only) of prep_x_kernel<false>: the five
+            // small loads, then the 21 matrix and 3 base loads stand back to back, the first wait
+            // after them is counted (s_waitcnt vmcnt(24): only the small loads), the division and
+            // dlim_threshold follow it, and the terms wait for the matrix in counted steps.
+            if constexpr (!kGen) asm volatile("" : "+v"(p1x), "+v"(p1y), "+v"(p1r), "+v"(rm), "+v"(dl) : : "memory");
             // pen_term (above), the same operations in the same order
-            const double x1 = pa.prev ? pa.prev[ii] : 0.0, y1 = pa.prev ? pa.prev[N + ii] : 0.0;
-            const double z1 = pa.prev ? pa.prev[2 * N + ii] / pa.tan_half_fov : 0.0;
-            const double rm = pa.rmax ? pa.rmax[ii] : 0.0;
-            const double T3 = pen_threshold(pa, ii);
+            const double x1 = p1x, y1 = p1y;
+            double z1 = pa.prev ? p1r / pa.tan_half_fov : 0.0;
+            // (pen_threshold's value: dlimT[ii], or the raw d_lim[ii] thresholded here)
+            double T3 = !pa.prev ? 0.0 : pa.dlimT ? dl : dlim_threshold(dl);
+            if constexpr (!kGen) asm volatile("" : "+v"(z1), "+v"(T3));
             uint32_t wdead = 0u;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
