@@ -88,7 +88,8 @@ __host__ __device__ __forceinline__ uint64_t mirror_check(uint64_t o, uint64_t i
 }
 
 // The pipelined MADS loop's update, by the wave that took the poll's argmin (every lane holds
-// bo, gidx): mac_mads_update's arithmetic (maxcover.hip; src/TDM_STATIC_opt.jl's NOMAD poll
+// bo, gidx): it restates mads_walk.h's mads_accept and mads_candidate, the arithmetic of
+// mac_mads_update (mads_driver.h), batched for the wave (src/TDM_STATIC_opt.jl's NOMAD poll
 // acceptance: a strictly better objective moves the incumbent and coarsens the mesh, else the mesh
 // is refined), with the same ltmads_entry values and per-variable adds, so the pipelined loop visits
 // the stepper's incumbents bit for bit. ell, f: the state before the poll.

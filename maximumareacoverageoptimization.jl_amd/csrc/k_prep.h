@@ -6,6 +6,7 @@
 
 #include "predicate.h"
 #include "mesh_key.h"
+#include "mads_walk.h"
 #include "k_common.h"
 
 #pragma clang fp contract(off)
@@ -79,35 +80,9 @@ __host__ __device__ __forceinline__ bool diag_rejects(double v, double b, double
 
 // ------------------------------------------------------------------ candidate sources
 
-// splitmix64 stream value number `idx` (1-based) after `state` (workloads.SplitMix64).
-__host__ __device__ __forceinline__ uint64_t splitmix_at(uint64_t state, uint64_t idx)
-{
-    uint64_t z = state + idx * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (the stream's draws, splitmix_at / ltmads_entry: mads_walk.h)
 
-__host__ __device__ __forceinline__ double splitmix_uniform_at(uint64_t state, uint64_t idx)
-{
-    return (double)(splitmix_at(state, idx) >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// Entry (r, c) of the lower-triangular LTMADS matrix L drawn from the stream at `state`
-// (workloads.ltmads_basis): diagonal sign(u_{r+1} < 0.5 ? -1 : 1) * 2^ell; strictly lower
-// entries uniform integers in [-(2^ell - 1), 2^ell - 1] from stream values n + 1 + r(r-1)/2 + c
-// (numpy's tril_indices order); zero above the diagonal.
-__host__ __device__ __forceinline__ double ltmads_entry(uint64_t state, int64_t n, int64_t b,
-                                                        int64_t r, int64_t c)
-{
-    if (r < c) return 0.0;
-    if (r == c) return (splitmix_uniform_at(state, (uint64_t)r + 1) < 0.5 ? -1.0 : 1.0) * (double)b;
-    const int64_t lo = -b + 1, span = 2 * b - 1;
-    const double u = splitmix_uniform_at(state, (uint64_t)(n + 1 + r * (r - 1) / 2 + c));
-    return (double)(lo + (int64_t)__builtin_floor(u * (double)span));
-}
-
-// The native MADS loop's state on the device when its polls are pipelined (maxcover.hip
+// The native MADS loop's state on the device when its polls are pipelined (mads_driver.h
 // mads_run_pipelined): the finalize of poll t applies poll t's update (k_final.h mads_step) and
 // poll t + 1's launches read the mesh index from here, so the host enqueues polls ahead of their
 // outcomes. ell < 0 (the mesh precision limit) stops the loop: every later launch returns at once.

@@ -1,4 +1,4 @@
-"""CPU: the whole-poll cons3 rejection (k_prep.h diag_rejects, used by maxcover.hip poll_rejected
+"""CPU: the whole-poll cons3 rejection (k_prep.h diag_rejects, used by mads_driver.h poll_rejected
 on the host and by the prep launch on the device) is exact: whenever every variable's diagonal
 step +-2^ell alone puts its UAV's own cons3 term above the threshold, the C oracle's cons3
 (src/TDM_Constraints.jl:54-75, oracle/ref_cpu.c ref_cons3) rejects every candidate of the

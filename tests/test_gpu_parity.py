@@ -1235,7 +1235,7 @@ def test_mads_best_buffer_device_exchange(ctx, pkg):
 ])
 def test_native_mads_pipelined_matches_stepper(ctx, pkg, N, n_iter, ell0, ell_max, cons3, stall):
     """mac_mads_run's pipelined loop (each poll's update applied on the device by its finalize,
-    polls enqueued ahead of their outcomes: maxcover.hip mads_run_pipelined) == the stepper driven
+    polls enqueued ahead of their outcomes: mads_driver.h mads_run_pipelined) == the stepper driven
     one poll at a time from Python (mac_mads_begin / _poll / _update, host update): same iterate
     bit for bit, objective, iteration and evaluation counts and status. `stall`: two entries
     under UAV 0 with every radius at r_max, so no poll can improve (a move keeps the union, a
