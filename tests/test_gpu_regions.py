@@ -498,9 +498,11 @@ PARENT_RECORD_KEYS = {
 TIMED = {"fire_s", "remove_s", "mads_s", "step_s", "mads_host_s"}
 
 
-def _replay(pkg, orc, D, x0, boxes, w_high, steps, N_iter, seed):
+def _replay(pkg, orc, D, x0, boxes, w_high, steps, N_iter, seed, poll_vars="xyr", granularity=None):
     """The MPC loop on the host: the oracle's fire, the numpy override at every push,
-    ref_remove_covered, and the per-trial-point MADS loop on the oracle's objective."""
+    ref_remove_covered, and the per-trial-point MADS loop on the oracle's objective. poll_vars
+    ("auto": FullSimulation.auto_poll_vars per step, as Simulation chooses) and granularity are passed
+    through to TDM_STATIC_opt.mads; each row then holds the step's poll_vars."""
     FS, TS, TC = pkg.FullSimulation, pkg.TDM_STATIC_opt, pkg.TDM_Constraints
     N = x0.size // 3
     tan = math.tan(FS.FOV / 2)
@@ -528,12 +530,19 @@ def _replay(pkg, orc, D, x0, boxes, w_high, steps, N_iter, seed):
         rec = lst.copy()
         rm = r_max.copy()
         c3 = TC.create_cons3(x_prev, FS.FOV, d_lim)
+        more = {}
+        if poll_vars != "xyr":
+            g = pkg._lib.mesh_granularity(granularity, x0.size)
+            more["poll_vars"] = poll_vars if poll_vars != "auto" else \
+                FS.auto_poll_vars(inp[2 * N:], r_max, 1.0 if g is None else g[2 * N:])
+        if granularity is not None:
+            more["granularity"] = granularity
         res = TS.mads(inp, lambda v: orc.ref_objective(v, rec, rm, 1e5), [c3], N_iter=N_iter, ell0=2,
-                      ell_max=6, seed=seed + t)
+                      ell_max=6, seed=seed + t, **more)
         x_out = res.x if res.x is not None else res.i
         outputs.append(x_out)
         row = dict(t=t, points=lst.shape[0], added=new.shape[0], kept=kept.size, f=res.x_cost,
-                   lst=lst.copy(), x=x_out, input=inp.copy())
+                   lst=lst.copy(), x=x_out, input=inp.copy(), **more)
         if boxes is not None:
             row["hi_total"], row["hi_uncovered"], row["hi_percentage"] = ref_percentage(pushed, lst, boxes)
         out.append(row)
