@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "predicate.h"
@@ -787,7 +788,11 @@ __device__ __forceinline__ void prep_block(const PrepArgs& a, int cw, unsigned c
 // a ninth wave that holds no UAV folds the chains (lane c: slot c's, sequential in UAV order). The
 // fold and the keys are exclusive branches, so the candidate values are dead on the folding
 // wave's path (80 VGPRs: two workgroups, 18 waves, fit a CU). Results are prep_block's bit for bit
-// (the same terms in the same order, the same keys and bound).
+// (the same terms in the same order, the same keys and bound). The matrix build's UAV waves are
+// VALU-bound behind the barrier (they end after the folding wave, tools/diag_prep.py), so it does
+// no arithmetic for a slot kPrepCX that holds no candidate (all but the first K - xbase workgroups)
+// and takes a packed slot's share of the bound from the key's integers; the generated builds are
+// the code they were.
 template <bool kGen, int kMesh = 0>   // (kMesh: as prep_block's)
 __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned char* lds)
 {
@@ -820,6 +825,9 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
     const bool excl = obj && (pa.prev || masked) && a.skip_failed;
     const bool iv = !fw && u < N;
     const int ii = min(u, N - 1);
+    // (matrix) slot PC holds a candidate in the first K - xbase workgroups alone: the others load it
+    // (clamped, so the loads issue as one straight run) and skip its arithmetic. Uniform.
+    const bool has7 = kGen || cand(PC) < K;
     MAC_PREP_STAMP(0);
     double v[NC][3];
     double base[3] = {0.0, 0.0, 0.0};   // candidate 0's values: the keys' base
@@ -922,6 +930,14 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
             uint32_t wdead = 0u;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
+                if constexpr (!kGen) {
+                    // an absent slot PC: no term (its row is read by no live fold lane), no failure
+                    // (wbad and wbadm's bit written as 0: a dead bit must not leak into `dead`)
+                    if (c == PC && !has7) {
+                        if (lane == 0) wbad[wid][c] = 0;
+                        continue;
+                    }
+                }
                 const double R2 = v[c][2];
                 double t = pa.rmax ? __builtin_fabs(R2 - rm) : 0.0;
                 if (pa.prev) {
@@ -1028,10 +1044,21 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
         // share of the displacement bound (k_fiw.h sup_box: live candidates only — r > 0, a finite
         // centre, not a cons3 failure; a NaN difference counts as +inf)
         double dmx = -__builtin_inf(), dmy = -__builtin_inf(), dmr = -__builtin_inf(), dml = -__builtin_inf();
+        // (matrix) the packed slots' share of the bound, as integers: a key that packs has proved
+        // v - base == (double)d bit for bit (key_int), so |x - x0|, |y - y0|, r - r0 and r0 - r are
+        // (double)|dx|, (double)|dy|, (double)dr and -(double)dr exactly (IEEE subtraction is
+        // antisymmetric), and the maximum is the same in either type. INT_MIN: none yet.
+        [[maybe_unused]] int mix = INT_MIN, miy = INT_MIN, mir = INT_MIN, mil = INT_MIN;
         uint32_t pk[NC];
         bool kb = false;   // (records) a key of this disk is inexact (k_index.h "Keys")
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
+            if constexpr (!kGen) {
+                if (c == PC && !has7) {   // an absent slot: no key, no share of the bound
+                    pk[c] = kKeyEsc;
+                    continue;
+                }
+            }
             const double x = v[c][0], y = v[c][1], r = v[c][2];
             int dx = 0, dy = 0, dr = 0;
             bool packs;
@@ -1054,18 +1081,53 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
                     a.keysT[(int64_t)(q * N + u) * a.ldk + cand(c)] = f;
                 }
             }
-            if (a.pd && iv && cand(c) < K && !((dead >> c) & 1u) && r > 0.0 && __builtin_isfinite(x) &&
-                __builtin_isfinite(y)) {
-                double ex = __builtin_fabs(x - base[0]), ey = __builtin_fabs(y - base[1]), er = r - base[2];
-                double el = base[2] - r;
-                if (!(ex <= kDblMax)) ex = __builtin_inf();
-                if (!(ey <= kDblMax)) ey = __builtin_inf();
-                if (!(er == er)) er = __builtin_inf();
-                if (!(el == el)) el = __builtin_inf();
-                dmx = fmax(dmx, ex);
-                dmy = fmax(dmy, ey);
-                dmr = fmax(dmr, er);
-                dml = fmax(dml, el);
+            if constexpr (kGen) {
+                if (a.pd && iv && cand(c) < K && !((dead >> c) & 1u) && r > 0.0 && __builtin_isfinite(x) &&
+                    __builtin_isfinite(y)) {
+                    double ex = __builtin_fabs(x - base[0]), ey = __builtin_fabs(y - base[1]), er = r - base[2];
+                    double el = base[2] - r;
+                    if (!(ex <= kDblMax)) ex = __builtin_inf();
+                    if (!(ey <= kDblMax)) ey = __builtin_inf();
+                    if (!(er == er)) er = __builtin_inf();
+                    if (!(el == el)) el = __builtin_inf();
+                    dmx = fmax(dmx, ex);
+                    dmy = fmax(dmy, ey);
+                    dmr = fmax(dmr, er);
+                    dml = fmax(dml, el);
+                }
+            } else {
+                // (a packed x or y is finite: its offset from the base is a finite double)
+                const bool live = a.pd && iv && cand(c) < K && !((dead >> c) & 1u) && r > 0.0;
+                if (live && packs) {
+                    mix = max(mix, abs(dx));
+                    miy = max(miy, abs(dy));
+                    mir = max(mir, dr);
+                    mil = max(mil, -dr);
+                }
+                // an escaped live slot: today's fp64 code; a wave without one executes none of it
+                const bool esc = live && !packs;
+                if (__ballot(esc) != 0) {
+                    if (esc && __builtin_isfinite(x) && __builtin_isfinite(y)) {   // (the generated builds' code above)
+                        double ex = __builtin_fabs(x - base[0]), ey = __builtin_fabs(y - base[1]), er = r - base[2];
+                        double el = base[2] - r;
+                        if (!(ex <= kDblMax)) ex = __builtin_inf();
+                        if (!(ey <= kDblMax)) ey = __builtin_inf();
+                        if (!(er == er)) er = __builtin_inf();
+                        if (!(el == el)) el = __builtin_inf();
+                        dmx = fmax(dmx, ex);
+                        dmy = fmax(dmy, ey);
+                        dmr = fmax(dmr, er);
+                        dml = fmax(dml, el);
+                    }
+                }
+            }
+        }
+        if constexpr (!kGen) {
+            if (a.pd) {
+                dmx = fmax(dmx, mix == INT_MIN ? -__builtin_inf() : (double)mix);
+                dmy = fmax(dmy, miy == INT_MIN ? -__builtin_inf() : (double)miy);
+                dmr = fmax(dmr, mir == INT_MIN ? -__builtin_inf() : (double)mir);
+                dml = fmax(dml, mil == INT_MIN ? -__builtin_inf() : (double)mil);
             }
         }
         if (kMesh != kMeshKeys && iv) {
@@ -1078,7 +1140,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
 #pragma unroll
                 for (int h = 0; h < PC / 2; ++h)
                     *reinterpret_cast<uint2*>(krow + k0 + 2 * h) = make_uint2(pk[2 * h], pk[2 * h + 1]);
-                if (cand(PC) < K) krow[cand(PC)] = pk[PC];
+                if (has7) krow[cand(PC)] = pk[PC];
             }
         }
         if (kGen && a.prec && iv) {
@@ -1127,6 +1189,7 @@ __device__ __forceinline__ void prep_block_x(const PrepArgs& a, int cw, unsigned
                 dred[wid][3] = dml;
             }
         }
+        MAC_PREP_STAMP(4);   // (diagnostic) wave 0 at the end of its keys and bound
     }
     if (a.pd) {   // the workgroup's displacement bound: the waves' shares in order
         lds_barrier();

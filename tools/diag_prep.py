@@ -49,4 +49,12 @@ if hasattr(L, "mac_diag_prep_read"):
     out["chain_phases_us_median"] = [float(v) for v in np.median(ph, axis=0)]
     out["chain_phases_us_max"] = [float(v) for v in ph.max(axis=0)]
     out["chain_phase_names"] = "per block: loads+terms (wave 0), barrier (wave 0), fold after the barrier (the folding wave)"
+    if nb == 1 and (p[:, 4] > p[:, 2]).all():
+        # prep_x_kernel: stamp 4 is wave 0 at the end of its keys and bound, the same barrier behind it
+        # as the fold (stamp 2); positive keys_minus_fold: the UAV waves outlast the folding wave
+        keys = (p[:, 4] - p[:, 2]) / 100.0
+        lead = (p[:, 4] - p[:, 3]) / 100.0
+        out["key_phase_us"] = {"median": float(np.median(keys)), "max": float(keys.max())}
+        out["keys_minus_fold_us"] = {"median": float(np.median(lead)), "min": float(lead.min()),
+                                     "max": float(lead.max())}
 print(json.dumps(out, indent=1))
