@@ -578,6 +578,70 @@ int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const
                           const mac_mads_mesh* mesh, const mac_prog* prog, double* x_inf_out,
                           mac_mads_prog_stats* pstats);
 
+/* The progressive barrier as a stepper: mac_mads_run_prog's loop one iteration at a time over the
+ * shard [shard_lo, shard_hi) of every centre's poll, for the sharded and the speculative multi-GPU
+ * loops (DESIGN.md section 4 "Progressive barrier": the shard-partial record). A poll reports a
+ * mac_prog_part: what steps 3-7 of the rule need from a subset S of the iteration's candidates
+ * g = centre K + k (objective +inf: not evaluated; NaN: counted, selects nothing). Every field merges
+ * exactly (a sum, an OR, a maximum, or a minimum under a total order with ties to the lower g), so the
+ * merged record depends neither on the partition nor on the merge order, and the iterates are
+ * mac_mads_run_prog's bit for bit.
+ *   tag        the 1-based iteration the record belongs to; bit 62: the loop ends there (done)
+ *   evaluated  objectives other than +inf                                                    sum
+ *   bestF      min (f, g) over h == 0 (bestF_g < 0: none)                                    min
+ *   dominates  an infeasible y with h <= I.h, f <= I.f, one of them strict (with an I only)  OR
+ *   h_below    max h over the infeasible y with h < I.h (with an I only; -1.0: none)         max
+ *   keep       min (f, h, g) over the infeasible y with h <= I.h (without an I: <= h_max)    min
+ *   drop       min (f, h, g) over the infeasible y with h < I.h (with an I only)             min
+ * The empty record: (tag, 0, +inf, -1, 0, -1.0, +inf, +inf, -1, +inf, +inf, -1). */
+typedef struct mac_prog_part {
+    int64_t tag;
+    int64_t evaluated;
+    double  bestF_f;
+    int64_t bestF_g;
+    int64_t dominates;
+    double  h_below;
+    double  keep_f, keep_h;
+    int64_t keep_g;
+    double  drop_f, drop_h;
+    int64_t drop_g;
+} mac_prog_part;              /* 96 B */
+
+/* mac_mads_begin_mesh under progressive constraints. prog = NULL or n_cons = 0: mac_mads_begin_mesh
+ * itself (a plain stepper). Otherwise mac_mads_run_prog's start: mac_prog's errors, h(x0) NaN and
+ * h(x0) > h_max0 (MAC_E_INVAL, naming mac_prog, before the context is touched; *out = NULL); F or I = x0.
+ * A prog stepper is stepped by the three calls below alone: mac_mads_poll / _update / _poll_ahead /
+ * _advance / _best_buffer return MAC_E_INVAL on it, as the calls below do on a plain stepper.
+ * mac_mads_destroy frees either. */
+int32_t mac_mads_begin_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max,
+                            double penalty, const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* params, int64_t shard_lo, int64_t shard_hi,
+                            mac_mads** out, const mac_cons* cons, const mac_mads_opts* opts,
+                            const mac_motion* motion, const mac_mads_mesh* mesh, const mac_prog* prog);
+/* The stepper's shard of the polls (F, then I) of the iteration that follows `ahead` iterations which
+ * are unsuccessful and leave I as it is (ahead = 0: the current one); the stepper stays as it is.
+ * Per centre what mac_mads_run_prog enqueues, over the shard; then prog_part_kernel (k_prog.h, one
+ * workgroup, one pass) and one read-back of its 96-byte record. The barrier's threshold: h_max at
+ * ahead = 0, else I.h with an I (what an unsuccessful iteration leaves). A centre cons3 rejects whole
+ * is not launched; an empty shard launches nothing and reports the empty record. *done = 1 (and bit
+ * 62 of the tag) when the loop ends before that iteration. */
+int32_t mac_mads_poll_prog(mac_mads* m, int32_t ahead, int32_t* done, mac_prog_part* part);
+/* n >= 1 records of one iteration merged into *out (out may be parts). Pure host arithmetic: no
+ * context. Unequal tags: MAC_E_INVAL. */
+int32_t mac_prog_merge(const mac_prog_part* parts, int32_t n, mac_prog_part* out);
+/* Applies the current iteration's merged record (tag = iterations done + 1, else MAC_E_INVAL): steps
+ * 3-7 from the record and the stepper's F, I and h_max, the incumbents rebuilt from (centre, k), ell,
+ * the counts and the stream advanced. *outcome (may be NULL): 0 dominating, 1 improving, 2
+ * unsuccessful. *chains (may be NULL): 1 when the iteration was unsuccessful and left I as it was, so
+ * that a record polled one iteration ahead applies next. */
+int32_t mac_mads_advance_prog(mac_mads* m, const mac_prog_part* merged, int32_t* outcome, int32_t* chains);
+/* mac_mads_run_prog's outputs from a prog stepper: x_out (may be NULL), x_inf_out (may be NULL), stats
+ * and pstats with the same meanings; pstats->evaluated sums the applied records' counts, while
+ * stats->feasible_evaluations counts what this stepper's own polls evaluated (its shard; polls ahead
+ * included). */
+int32_t mac_mads_result_prog(mac_mads* m, double* x_out, double* x_inf_out, mac_mads_stats* stats,
+                             mac_mads_prog_stats* pstats);
+
 /* fp32 candidates (config 3's "fp32" caller path; SURVEY 8(b) "*_f32: coords f32, accum f64"):
  * the candidate matrix (and prev) are uploaded as floats and widened exactly on the device;
  * coverage is then the reference's fp64 predicate on those doubles, areas accumulate in fp64 /

@@ -18,7 +18,8 @@ is what the parity tests exercise. See INTEGRATION.md.
 module MaxCoverAMD
 
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
-       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacProg, MadsProgStats, MacCons, MacMotion, cons_mask,
+       poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacProg, MadsProgStats, MacProgPart, MadsProgStepper,
+       mads_prog_stepper, poll_prog!, advance_prog!, prog_merge, result_prog, close_prog!, MacCons, MacMotion, cons_mask,
        set_mesh_keys!, set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
@@ -593,6 +594,123 @@ function mads_run(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext;
         end
     end
     return x, st[]
+end
+
+"""
+MacProgPart — mac_prog_part (include/maxcover.h), 96 bytes: the shard-partial record of one iteration of
+the progressive barrier, what a rank's poll reports and what the ranks exchange and merge. `tag`: the
+1-based iteration, bit 62 set when the loop ends there.
+"""
+struct MacProgPart
+    tag::Int64
+    evaluated::Int64
+    bestF_f::Float64
+    bestF_g::Int64
+    dominates::Int64
+    h_below::Float64
+    keep_f::Float64
+    keep_h::Float64
+    keep_g::Int64
+    drop_f::Float64
+    drop_h::Float64
+    drop_g::Int64
+end
+
+"A prog stepper's handle (mac_mads*) with its context and size; `close_prog!` frees it."
+mutable struct MadsProgStepper
+    handle::Ptr{Cvoid}
+    ctx::MacContext
+    n::Int
+end
+
+"""
+mads_prog_stepper(x0, r_max, ctx; prog, shard = nothing, ...) — mac_mads_begin_prog: `mads_run(...; prog)`'s
+loop one iteration at a time over the candidate shard `shard = (lo, hi)` (0-based, half-open; nothing: the
+whole poll) of every centre's poll. Drive it with `poll_prog!`, `prog_merge` over the ranks' records and
+`advance_prog!`. The keywords are `mads_run`'s; every rank passes the same ones. Like the rest of the shim
+these wrappers have not been executed here.
+"""
+function mads_prog_stepper(x0::Vector{Float64}, r_max::Vector{Float64}, ctx::MacContext; prog::MacProg,
+                           shard = nothing, penalty::Float64 = 1e5,
+                           prev::Union{Nothing,Vector{Float64}} = nothing,
+                           d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0,
+                           n_iter::Integer = 100, ell0::Integer = 2, ell_max::Integer = 6,
+                           seed::Integer = 20250216, cons::Union{Nothing,MacCons} = nothing,
+                           poll_vars::Symbol = :xyr, motion::Union{Nothing,MacMotion} = nothing,
+                           granularity = nothing)
+    length(prog.member) == length(prog.limit) == length(x0) ÷ 3 ||
+        throw(ArgumentError("prog: member and limit hold N values each"))
+    opts = MadsOpts(poll_vars)
+    g = granularity === nothing ? nothing : mesh_granularity(granularity, length(x0))
+    n_p = poll_vars == :xy ? 2 * (length(x0) ÷ 3) : length(x0)
+    lo, hi = shard === nothing ? (0, 2 * n_p) : shard
+    prm = Ref(MadsParams(n_iter, ell0, ell_max, UInt64(seed)))
+    pprev = prev === nothing ? Ptr{Float64}(C_NULL) : pointer(prev)
+    pdlim = d_lim === nothing ? Ptr{Float64}(C_NULL) : pointer(d_lim)
+    rcons = cons === nothing ? nothing : Ref(cons)
+    rmot = motion === nothing ? nothing : Ref(CMotion(motion))
+    rmesh = g === nothing ? nothing : Ref(MacMadsMesh(pointer(g), 0))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve prev d_lim motion g prog rcons rmot rmesh begin
+        pcons = rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons)
+        pmot = rmot === nothing ? Ptr{CMotion}(C_NULL) : Base.unsafe_convert(Ptr{CMotion}, rmot)
+        pmesh = rmesh === nothing ? Ptr{MacMadsMesh}(C_NULL) : Base.unsafe_convert(Ptr{MacMadsMesh}, rmesh)
+        cp = Ref(CProg(pointer(prog.member), pointer(prog.limit), prog.n_cons, Int32(0), prog.h_max0))
+        check(ccall((:mac_mads_begin_prog, libmaxcover), Int32,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64},
+                     Float64, Ref{MadsParams}, Int64, Int64, Ref{Ptr{Cvoid}}, Ptr{MacCons}, Ref{MadsOpts},
+                     Ptr{CMotion}, Ptr{MacMadsMesh}, Ref{CProg}),
+                    ctx, x0, length(x0), r_max, penalty, pprev, pdlim, tan_half_fov, prm, lo, hi, h,
+                    pcons, Ref(opts), pmot, pmesh, cp))
+    end
+    return MadsProgStepper(h[], ctx, length(x0))
+end
+
+"poll_prog!(st, ahead = 0) — mac_mads_poll_prog: (done, part) of the stepper's shard, `ahead` chaining iterations on."
+function poll_prog!(st::MadsProgStepper, ahead::Integer = 0)
+    done = Ref{Int32}(0)
+    part = Ref{MacProgPart}()
+    check(ccall((:mac_mads_poll_prog, libmaxcover), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{MacProgPart}),
+                st.handle, ahead, done, part))
+    return done[] != 0, part[]
+end
+
+"prog_merge(parts) — mac_prog_merge: the records of one iteration merged (exact, in any order; no context)."
+function prog_merge(parts::Vector{MacProgPart})
+    out = Ref{MacProgPart}()
+    check(ccall((:mac_prog_merge, libmaxcover), Int32, (Ptr{MacProgPart}, Int32, Ref{MacProgPart}),
+                parts, length(parts), out))
+    return out[]
+end
+
+"advance_prog!(st, merged) — mac_mads_advance_prog: (outcome 0 / 1 / 2, chains::Bool)."
+function advance_prog!(st::MadsProgStepper, merged::MacProgPart)
+    outcome = Ref{Int32}(0)
+    chains = Ref{Int32}(0)
+    check(ccall((:mac_mads_advance_prog, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ref{MacProgPart}, Ref{Int32}, Ref{Int32}), st.handle, Ref(merged), outcome, chains))
+    return outcome[], chains[] != 0
+end
+
+"result_prog(st) — mac_mads_result_prog: (x, stats::MadsStats, x_infeasible or nothing, pstats::MadsProgStats)."
+function result_prog(st::MadsProgStepper)
+    x = Vector{Float64}(undef, st.n)
+    xi = fill(NaN, st.n)
+    s = Ref{MadsStats}()
+    ps = Ref{MadsProgStats}()
+    check(ccall((:mac_mads_result_prog, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{MadsStats}, Ref{MadsProgStats}),
+                st.handle, x, xi, s, ps))
+    return x, s[], (ps[].has_infeasible != 0 ? xi : nothing), ps[]
+end
+
+"close_prog!(st) — mac_mads_destroy."
+function close_prog!(st::MadsProgStepper)
+    if st.handle != C_NULL
+        ccall((:mac_mads_destroy, libmaxcover), Cvoid, (Ptr{Cvoid},), st.handle)
+        st.handle = C_NULL
+    end
+    return nothing
 end
 
 """

@@ -158,8 +158,11 @@ class Simulation:
     ``h_max0`` (None: h at each step's MADS input). An entry is a constraint carrying ``mac_prog``
     data, or a factory called once with the simulation's own ``r_max`` array (the one the r_max rule
     updates): ``TDM_Constraints.create_cons1_progressive``, or
-    ``functools.partial(create_cons_progressive, i)``. A callable without device data, or a shard of
-    more than one rank, is refused (ValueError): the barrier runs in the single-GPU native loop only.
+    ``functools.partial(create_cons_progressive, i)``. A callable without device data is refused
+    (ValueError). With a shard the step runs dist.mads_prog_loop_speculative (more than one rank and
+    ``speculate`` None or True) or dist.mads_prog_loop on Context.mads_prog_stepper, over a
+    dist.RcclProgGather (the default on a cuda ``device``) or a dist.ProgGather; a given gather that is
+    neither is refused (ValueError) before the context is used.
     Each record then gains ``h`` (of the step's output), ``has_feasible`` and the counts
     ``dominating`` / ``improving`` / ``unsuccessful``. ``penalty``: the objective's weight on
     sum |R_i - r_max_i| (src/TDM_STATIC_opt.jl:97), 1e5 as in the reference; 0 leaves the altitude to
@@ -203,7 +206,7 @@ class Simulation:
                       else np.asarray(r_max, dtype=np.float64).copy())
         self.penalty = float(penalty)
         self.h_max0 = h_max0
-        self.cons_prog = self._cons_prog(cons_prog, shard)
+        self.cons_prog = self._cons_prog(cons_prog, shard, gather)
         self.fire, self.firepoints = fire, firepoints
         self.N_iter, self.seed, self.ell0, self.ell_max = N_iter, seed, ell0, ell_max
         self.shard = shard          # (rank, world) or None: the whole poll on this GPU
@@ -215,11 +218,15 @@ class Simulation:
         multi = shard is not None and shard[1] > 1
         if speculate is None:
             from .dist import SpecGather
-            speculate = multi and (gather is None or isinstance(gather, SpecGather))
+            # (a prog gather serves either loop: speculative unless speculate=False)
+            speculate = multi and (gather is None or bool(self.cons_prog) or isinstance(gather, SpecGather))
         if multi and gather is None:
-            from .dist import RcclShardGather, RcclSpecGather, SpecGather, make_gather
+            from .dist import (ProgGather, RcclProgGather, RcclShardGather, RcclSpecGather, SpecGather,
+                               make_gather)
             dev = device if device is not None else "cpu"
-            if str(dev).startswith("cuda"):   # libmaxcover's own RCCL communicator on ctx
+            if self.cons_prog:   # the 96-byte record, whichever loop
+                gather = RcclProgGather(ctx, dev) if str(dev).startswith("cuda") else ProgGather(dev)
+            elif str(dev).startswith("cuda"):   # libmaxcover's own RCCL communicator on ctx
                 gather = RcclSpecGather(ctx, dev) if speculate else RcclShardGather(ctx, dev)
             else:
                 gather = SpecGather(dev) if speculate else make_gather(dev)
@@ -239,7 +246,7 @@ class Simulation:
         self.outputs = []
         self.records = []
 
-    def _cons_prog(self, cons_prog, shard):
+    def _cons_prog(self, cons_prog, shard, gather=None):
         """The progressive constraints bound to the simulation's r_max (an empty list: none)."""
         from .TDM_Constraints import merge_mac_prog
         if callable(cons_prog):
@@ -255,9 +262,12 @@ class Simulation:
                 raise ValueError("cons_prog: a progressive constraint without device data (mac_prog) cannot "
                                  "run in the native MADS driver")
             out.append(c)
-        if out and shard is not None and shard[1] > 1:
-            raise ValueError("cons_prog: the progressive barrier runs on one GPU only (shard of "
-                             f"{shard[1]} ranks given)")
+        if out and shard is not None and shard[1] > 1 and gather is not None:
+            from .dist import ProgGather, RcclProgGather
+            if not isinstance(gather, (ProgGather, RcclProgGather)):
+                raise ValueError("cons_prog: a shard of more than one rank exchanges the barrier's 96-byte "
+                                 "record: gather must be a dist.ProgGather or dist.RcclProgGather, not "
+                                 f"{type(gather).__name__}")
         if out and merge_mac_prog(out, self.N)[1]:
             raise ValueError("cons_prog: the constraints do not fit one mac_prog (different limits, or "
                              "more than 32)")
@@ -333,7 +343,17 @@ class Simulation:
             from .TDM_Constraints import merge_mac_prog
             kw["prog"] = merge_mac_prog(self.cons_prog, N)[0]
             kw["h_max0"] = self.h_max0
-        if self.shard is None or self.shard[1] == 1:
+        if self.cons_prog and self.shard is not None:   # (a shard of one rank: the stepper's loop, no exchange)
+            from .dist import mads_prog_loop, mads_prog_loop_speculative, shard_range
+            n_polled = single_input.size if pvars == "xyr" else 2 * N
+            sh = None if self.speculate else shard_range(2 * n_polled, *self.shard)
+            stepper = ctx.mads_prog_stepper(single_input, self.r_max, self.penalty, shard=sh, **kw)
+            try:
+                loop = mads_prog_loop_speculative if self.speculate else mads_prog_loop
+                x_out, st = loop(stepper, self.gather)
+            finally:
+                stepper.close()
+        elif self.shard is None or self.shard[1] == 1:
             x_out, st = ctx.mads_run(single_input, self.r_max, self.penalty, **kw)
         elif self.speculate:
             from .dist import mads_loop_speculative

@@ -447,6 +447,242 @@ class PollStepper:
                                "status": 0 if self.ell < 0 else 1}
 
 
+# ---------------------------------------------------------------- the barrier's shard-partial record
+# Plain-Python mirrors of csrc/prog_rule.h (DESIGN.md section 4 "Progressive barrier"): a record is the
+# tuple of mac_prog_part's twelve fields in their order, the scalars are prog_select's (F_f, I_f, I_h,
+# h_max) with None for an incumbent that does not exist.
+
+PROG_TAG_DONE = 1 << 62
+PROG_NEW_I_NONE, PROG_NEW_I_OLD = -1, -2
+
+
+def _less2(f, g, f2, g2):
+    return g >= 0 and (g2 < 0 or f < f2 or (f == f2 and g < g2))
+
+
+def _less3(f, h, g, f2, h2, g2):
+    return g >= 0 and (g2 < 0 or f < f2 or (f == f2 and (h < h2 or (h == h2 and g < g2))))
+
+
+def prog_part_empty(tag: int = 0):
+    inf = float("inf")
+    return (int(tag), 0, inf, -1, 0, -1.0, inf, inf, -1, inf, inf, -1)
+
+
+def prog_part(F_f, I_f, I_h, h_max, cands, tag: int = 0):
+    """prog_part_fold over ``cands`` = [(f, h, g), ...] (g = centre K + k, any order): an objective of
+    +inf is "not evaluated", a NaN one is counted and selects nothing."""
+    tag, ev, bf, bg, dom, hb, kf, kh, kg, df, dh, dg = prog_part_empty(tag)
+    has_I = I_h is not None
+    thr = I_h if has_I else h_max
+    for f, h, g in cands:
+        f, h, g = float(f), float(h), int(g)
+        if f == float("inf"):
+            continue
+        ev += 1
+        if f != f:
+            continue
+        if h == 0.0:
+            if _less2(f, g, bf, bg):
+                bf, bg = f, g
+        elif h > 0.0:
+            if has_I:
+                if h <= I_h and f <= I_f and (h < I_h or f < I_f):
+                    dom = 1
+                if h < I_h:
+                    if h > hb:
+                        hb = h
+                    if _less3(f, h, g, df, dh, dg):
+                        df, dh, dg = f, h, g
+            if h <= thr and _less3(f, h, g, kf, kh, kg):
+                kf, kh, kg = f, h, g
+    return (tag, ev, bf, bg, dom, hb, kf, kh, kg, df, dh, dg)
+
+
+def prog_merge(parts):
+    """prog_part_merge over the records of one iteration (unequal tags: ValueError)."""
+    parts = [tuple(p) for p in parts]
+    if not parts:
+        raise ValueError("prog_merge: no record")
+    tag, ev, bf, bg, dom, hb, kf, kh, kg, df, dh, dg = parts[0]
+    for p in parts[1:]:
+        if p[0] != tag:
+            raise ValueError(f"prog_merge: records of different iterations (tags {tag} and {p[0]})")
+        ev += p[1]
+        if _less2(p[2], p[3], bf, bg):
+            bf, bg = p[2], p[3]
+        dom |= p[4]
+        hb = p[5] if p[5] > hb else hb
+        if _less3(p[6], p[7], p[8], kf, kh, kg):
+            kf, kh, kg = p[6:9]
+        if _less3(p[9], p[10], p[11], df, dh, dg):
+            df, dh, dg = p[9:12]
+    return (tag, ev, bf, bg, dom, hb, kf, kh, kg, df, dh, dg)
+
+
+def prog_finish(part, F_f, I_f, I_h, h_max):
+    """prog_finish: ProgRec's eight fields (outcome | 256 when bestF replaces F, bestF_f, bestF_g,
+    newI_f, newI_h, newI_g (-1: none, -2: the old one), h_new, evaluated) from the merged record."""
+    _, ev, bf, bg, dom, hb, kf, kh, kg, df, dh, dg = part
+    has_I = I_h is not None
+    improves = bg >= 0 and (F_f is None or bf < F_f)
+    dominating = improves or dom != 0
+    improving = (not dominating) and has_I and hb > 0.0
+    h_new = hb if improving else (I_h if has_I else h_max)
+    nf, nh, ng = (df, dh, dg) if improving else (kf, kh, kg)
+    if has_I and I_h <= h_new and not (ng >= 0 and (nf < I_f or (nf == I_f and nh < I_h))):
+        nf, nh, ng = I_f, I_h, PROG_NEW_I_OLD
+    code = (0 if dominating else 1 if improving else 2) | (256 if improves else 0)
+    return (code, bf, bg, nf, nh, ng, h_new, ev)
+
+
+def prog_chains(rec, has_I: bool) -> bool:
+    """prog_chains: the iteration was unsuccessful and left I as it was (no I before and none after
+    counts), so the poll one iteration ahead was the right one."""
+    return (rec[0] & 255) == 2 and (rec[5] == PROG_NEW_I_OLD or (not has_I and rec[5] == PROG_NEW_I_NONE))
+
+
+class ProgPollStepper:
+    """Host mirror of the native prog stepper (mac_mads_begin_prog / _poll_prog / _advance_prog,
+    include/maxcover.h), driven by ``dist.mads_prog_loop`` and ``dist.mads_prog_loop_speculative``:
+    ``mads_prog``'s sequence (same stream, same rule), of which this stepper evaluates the shard
+    [lo, hi) of every centre's poll as ``mads_prog`` evaluates a whole one. ``poll(ahead)`` ->
+    (done, record) leaves the stepper as it is; ``advance(record)`` applies the iteration's merged
+    record -> (outcome, chains). ``result()``: a MADSResult as ``mads_prog`` returns it."""
+
+    def __init__(self, input, obj, cons_ext=(), cons_prog=(), h_max0=None, N_iter: int = 100,
+                 ell0: int = 2, ell_max: int = 6, seed: int = 20250216, shard=None,
+                 poll_vars: str = "xyr", granularity=None):
+        x0 = np.asarray(input, dtype=np.float64).copy()
+        self.n = polled_count(x0.size, poll_vars)
+        self.g = mesh_granularity(granularity, x0.size)
+        self.obj, self.cons, self.progs = obj, list(cons_ext), list(cons_prog)
+        if not self.progs:
+            raise ValueError("ProgPollStepper: cons_prog is empty (use PollStepper)")
+        self.dev_prog = None
+        if hasattr(obj, "poll"):
+            self.dev_prog, plain = merge_mac_prog(self.progs, x0.size // 3)
+            if plain:
+                self.dev_prog = None
+        self.N_iter, self.ell, self.ell_max = N_iter, ell0, ell_max
+        self.rng = SplitMix64(seed)
+        self.it = 0
+        self.K = 2 * self.n
+        self.lo, self.hi = (0, self.K) if shard is None else (int(shard[0]), int(shard[1]))
+        self.shard = (self.lo, self.hi)
+        self.res = MADSResult()
+        h0 = float(self._h_of(x0[None, :])[0])
+        if h0 != h0:
+            raise ValueError("cons_prog: h(x0) is NaN")
+        given = h_max0 is not None and float(h_max0) >= 0.0
+        self.h_max = float(h_max0) if given else (h0 if h0 > 0.0 else np.inf)
+        if h0 > self.h_max:
+            raise ValueError(f"cons_prog: h(x0) = {h0} > h_max0 = {self.h_max}")
+        f0 = float(self._evaluate(x0[None, :])[0]) if all(bool(c(x0)) for c in self.cons) else np.inf
+        self.res.status.function_evaluations += 1
+        self.F = (x0, f0) if h0 == 0.0 else None
+        self.I = None if h0 == 0.0 else (x0, f0, h0)
+
+    def _h_of(self, X):
+        if self.dev_prog is not None:
+            return np.asarray(self.obj.ctx.prog_h(X, self.dev_prog), dtype=np.float64)
+        return np.array([prog_h([c(v) for c in self.progs]) for v in X], dtype=np.float64)
+
+    def _evaluate(self, X):
+        if hasattr(self.obj, "poll"):
+            return np.asarray(self.obj.poll(X)[2], dtype=np.float64)
+        return np.array([self.obj(v) for v in X], dtype=np.float64)
+
+    def _draws(self) -> int:
+        n = self.n
+        return n + n * (n - 1) // 2 + 2 * n   # ltmads_basis's stream values per iteration
+
+    def _basis(self, ahead: int):
+        rng = SplitMix64()
+        with np.errstate(over="ignore"):
+            rng.state = self.rng.state + np.uint64(ahead * self._draws()) * np.uint64(0x9E3779B97F4A7C15)
+        return scaled_basis(ltmads_basis(self.n, self.ell - ahead, rng).astype(np.float64), self.g)
+
+    def _centres(self):
+        return [p[0] for p in (self.F, self.I) if p is not None]
+
+    def _scalars(self):
+        return (None if self.F is None else self.F[1], None if self.I is None else self.I[1],
+                None if self.I is None else self.I[2], self.h_max)
+
+    def poll(self, ahead: int = 0):
+        tag = self.it + ahead + 1
+        if self.it + ahead >= self.N_iter or self.ell - ahead < 0:
+            return True, prog_part_empty(tag | PROG_TAG_DONE)
+        F_f, I_f, I_h, h_max = self._scalars()
+        if ahead > 0 and I_h is not None:   # what an unsuccessful iteration leaves
+            h_max = I_h
+        B = self._basis(ahead)
+        cands = []
+        for c, xc in enumerate(self._centres()):
+            X = poll_matrix(xc, B)[self.lo:self.hi]
+            if X.shape[0] == 0:
+                continue
+            h = self._h_of(X)
+            keep = np.array([all(bool(q(v)) for q in self.cons) for v in X], dtype=bool)
+            keep &= ~(h != h) & ~(h > h_max)
+            idx = np.flatnonzero(keep)
+            if idx.size:
+                fv = self._evaluate(X[idx])
+                cands += [(float(f), float(h[k]), c * self.K + self.lo + int(k)) for k, f in zip(idx, fv)]
+        return False, prog_part(F_f, I_f, I_h, h_max, cands, tag)
+
+    def advance(self, part):
+        part = tuple(part)
+        if part[0] != self.it + 1:
+            raise ValueError(f"ProgPollStepper.advance: the record's tag {part[0]} is not iteration {self.it + 1}")
+        st = self.res.status
+        centres = self._centres()
+        B = self._basis(0)
+        had_I = self.I is not None
+        rec = prog_finish(part, *self._scalars())
+        code, bestF_f, bestF_g, newI_f, newI_h, newI_g, h_new, evaluated = rec
+        point = lambda g: poll_matrix(centres[g // self.K], B)[g % self.K].copy()   # noqa: E731
+        newF = (point(bestF_g), bestF_f) if code & 256 else None
+        newI = (point(newI_g), newI_f, newI_h) if newI_g >= 0 else None
+        if newF is not None:
+            self.F = newF
+        if newI is not None:
+            self.I = newI
+        elif newI_g == PROG_NEW_I_NONE:
+            self.I = None
+        self.h_max = h_new
+        st.two_centre_polls += len(centres) == 2
+        st.function_evaluations += self.K * len(centres)
+        st.evaluated += evaluated
+        outcome = ("dominating", "improving", "unsuccessful")[code & 255]
+        if outcome == "dominating":
+            self.ell = min(self.ell + 1, self.ell_max)
+            st.dominating += 1
+            st.successes += 1
+        elif outcome == "improving":
+            st.improving += 1
+        else:
+            self.ell -= 1
+            st.unsuccessful += 1
+        F, I = self.F, self.I
+        self.res.history.append((outcome, None if F is None else F[0].copy(), None if F is None else F[1],
+                                 None if I is None else I[0].copy(), None if I is None else I[1],
+                                 None if I is None else I[2], self.h_max, len(centres)))
+        self.rng.next_u64(self._draws())   # the iteration's stream values
+        self.it += 1
+        return outcome, prog_chains(rec, had_I)
+
+    def result(self) -> MADSResult:
+        res, st = self.res, self.res.status
+        st.iteration = self.it
+        st.optimization_status = "MeshPrecisionLimit" if self.ell < 0 else "IterationLimit"
+        res.h_max = self.h_max
+        res.x, res.x_cost = self.F if self.F is not None else (None, np.inf)
+        res.i, res.i_cost, res.i_h = self.I if self.I is not None else (None, np.inf, None)
+        return res
+
+
 def optimize(input, obj, cons_ext, cons_prog, N_iter: int):
     """src/TDM_STATIC_opt.jl:118-222: returns (p.x if feasible else p.i, runtime_total)."""
     p = mads(input, obj, cons_ext, N_iter, cons_prog=tuple(cons_prog or ()))

@@ -87,6 +87,8 @@ EXPORTS = (
     "mac_mads_run_motion", "mac_mads_begin_motion",
     "mac_mads_run_mesh", "mac_mads_begin_mesh", "mac_profile_fused",
     "mac_prog_h_f64", "mac_mads_run_prog", "mac_diag_poll_report",
+    "mac_mads_begin_prog", "mac_mads_poll_prog", "mac_prog_merge", "mac_mads_advance_prog",
+    "mac_mads_result_prog",
 )
 
 MAC_REGIONS_MAX = 64
@@ -271,6 +273,40 @@ class MadsProgStats(ctypes.Structure):
                 ("evaluated", ctypes.c_int64)]
 
 
+class ProgPart(ctypes.Structure):
+    """mac_prog_part (include/maxcover.h): the shard-partial record of one iteration of the
+    progressive barrier. ``tag``: the 1-based iteration, bit 62 set when the loop ends there."""
+    _fields_ = [("tag", ctypes.c_int64), ("evaluated", ctypes.c_int64),
+                ("bestF_f", ctypes.c_double), ("bestF_g", ctypes.c_int64),
+                ("dominates", ctypes.c_int64), ("h_below", ctypes.c_double),
+                ("keep_f", ctypes.c_double), ("keep_h", ctypes.c_double), ("keep_g", ctypes.c_int64),
+                ("drop_f", ctypes.c_double), ("drop_h", ctypes.c_double), ("drop_g", ctypes.c_int64)]
+
+    def words(self) -> np.ndarray:
+        """The record's 12 words as float64 (raw bits: what a gather exchanges)."""
+        return np.frombuffer(bytes(self), dtype=np.float64).copy()
+
+    @classmethod
+    def from_words(cls, w) -> "ProgPart":
+        return cls.from_buffer_copy(np.ascontiguousarray(w, dtype=np.float64).tobytes())
+
+    def as_tuple(self):
+        return tuple(getattr(self, k) for k, _ in self._fields_)
+
+
+PROG_TAG_DONE = 1 << 62
+
+
+def prog_merge(parts) -> ProgPart:
+    """mac_prog_merge: the records of one iteration (ProgPart, or 12 float64 words each) merged into one;
+    exact, in any order. Unequal tags: MaxCoverError (MAC_E_INVAL). Needs no context."""
+    ps = [p if isinstance(p, ProgPart) else ProgPart.from_words(p) for p in parts]
+    arr = (ProgPart * max(len(ps), 1))(*ps)
+    out = ProgPart()
+    _check(load_library().mac_prog_merge(arr, len(ps), ctypes.byref(out)))
+    return out
+
+
 def make_prog(prog=None, member=None, limit=None, n_cons: int | None = None,
               h_max0: float | None = None) -> Prog | None:
     """A Prog from a Prog, a mapping / object with member, limit, n_cons (and h_max0) fields (e.g.
@@ -444,6 +480,16 @@ def _declare(L: ctypes.CDLL) -> None:
                                ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts), ctypes.POINTER(Motion),
                                ctypes.POINTER(MadsMesh), ctypes.POINTER(Prog), _dp,
                                ctypes.POINTER(MadsProgStats)], _i32),
+        "mac_mads_begin_prog": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
+                                 ctypes.POINTER(MadsParams), _i64, _i64, ctypes.POINTER(_vp),
+                                 ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
+                                 ctypes.POINTER(Motion), ctypes.POINTER(MadsMesh), ctypes.POINTER(Prog)], _i32),
+        "mac_mads_poll_prog": ([_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(ProgPart)], _i32),
+        "mac_prog_merge": ([ctypes.POINTER(ProgPart), _i32, ctypes.POINTER(ProgPart)], _i32),
+        "mac_mads_advance_prog": ([_vp, ctypes.POINTER(ProgPart), ctypes.POINTER(_i32),
+                                   ctypes.POINTER(_i32)], _i32),
+        "mac_mads_result_prog": ([_vp, _dp, _dp, ctypes.POINTER(MadsStats),
+                                  ctypes.POINTER(MadsProgStats)], _i32),
         "mac_mads_poll": ([_vp, ctypes.POINTER(_i32), _dp, _i64p], _i32),
         "mac_mads_update": ([_vp, ctypes.c_double, _i64], _i32),
         "mac_mads_poll_ahead": ([_vp, _i32, ctypes.POINTER(_i32), _dp, _i64p, _i64p], _i32),
@@ -1114,13 +1160,27 @@ class Context:
         ``poll_vars``: as mads_run's (n_p = 3N for "xyr", 2N for "xy": mac_mads_begin_opts).
         ``motion``: as mads_run's (mac_mads_begin_motion; the same on every rank).
         ``granularity``: as mads_run's (mac_mads_begin_mesh; the same on every rank).
-        ``prog``: refused (ValueError): the stepper, and with it the sharded and speculative loops,
-        has no progressive barrier; use mads_run."""
+        ``prog``: refused (ValueError): this stepper exchanges a 16-byte best, which the progressive
+        barrier cannot be decided from; use mads_prog_stepper (or mads_run)."""
         if prog is not None:
-            raise ValueError("mads_stepper: prog (progressive constraints) is not supported by the "
-                             "stepper; use mads_run(prog=)")
+            raise ValueError("mads_stepper: prog (progressive constraints) is not supported by this "
+                             "stepper; use mads_prog_stepper(prog=) or mads_run(prog=)")
         st = MadsStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
                          ell_max, seed, shard, cons, poll_vars, motion, granularity)
+        self._steppers.add(st)
+        return st
+
+    def mads_prog_stepper(self, x0, r_max, penalty: float = 1e5, prev=None, d_lim=None,
+                          tan_half_fov: float = 1.0, n_iter: int = 100, ell0: int = 2,
+                          ell_max: int = 6, seed: int = 20250216, shard=None,
+                          cons=None, poll_vars: str = "xyr", motion=None,
+                          granularity=None, prog=None, h_max0=None) -> "MadsProgStepper":
+        """mac_mads_begin_prog: mads_run(prog=)'s loop one iteration at a time over the candidate shard
+        ``shard`` = (lo, hi) of every centre's poll (None: the whole poll), for dist.mads_prog_loop and
+        dist.mads_prog_loop_speculative. The other keywords: as mads_stepper's and mads_run's; every
+        rank passes the same ones. ``prog`` must hold a constraint (n_cons > 0)."""
+        st = MadsProgStepper(self, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter, ell0,
+                             ell_max, seed, shard, cons, poll_vars, motion, granularity, prog, h_max0)
         self._steppers.add(st)
         return st
 
@@ -1398,6 +1458,84 @@ class MadsStepper:
         st = MadsStats()
         _check(self._L.mac_mads_result(self._h, _ptr(out), ctypes.byref(st)))
         return out, {k: getattr(st, k) for k, _ in MadsStats._fields_}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._L.mac_mads_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MadsProgStepper:
+    """mac_mads_begin_prog / _poll_prog / _advance_prog / _result_prog (include/maxcover.h): poll(ahead)
+    -> (done, ProgPart) over this stepper's shard of the iteration ``ahead`` chaining iterations on;
+    advance(part) with the record merged over all shards -> (outcome, chains); result() -> (x, stats)
+    with mads_run(prog=)'s keys. dist.mads_prog_loop and dist.mads_prog_loop_speculative drive it."""
+
+    OUTCOMES = ("dominating", "improving", "unsuccessful")
+
+    def __init__(self, ctx: Context, x0, r_max, penalty, prev, d_lim, tan_half_fov, n_iter,
+                 ell0, ell_max, seed, shard, cons=None, poll_vars: str = "xyr", motion=None,
+                 granularity=None, prog=None, h_max0=None):
+        pvars = poll_vars_code(poll_vars)
+        x = _f64(x0)
+        g = mesh_granularity(granularity, x.size)   # (validated before the library is touched)
+        pg = make_prog(prog, h_max0=h_max0)
+        if pg is None or pg.n_cons <= 0:
+            raise ValueError("mads_prog_stepper: prog must hold a progressive constraint (use mads_stepper)")
+        if pg.n_uav != x.size // 3:
+            raise ValueError("prog: member and limit hold N values each")
+        self._L = ctx._L
+        self._ctx = ctx   # keeps the context alive while the stepper lives
+        rm = _f64(r_max)
+        pv = _f64(prev) if prev is not None else None
+        dl = _f64(d_lim) if d_lim is not None else None
+        self.n = x.size
+        self.poll_vars = poll_vars
+        self.n_polled = x.size if pvars == MAC_POLL_XYR else 2 * (x.size // 3)
+        self.candidates = 2 * self.n_polled
+        lo, hi = (0, self.candidates) if shard is None else (int(shard[0]), int(shard[1]))
+        self.shard = (lo, hi)
+        prm = MadsParams(int(n_iter), int(ell0), int(ell_max), int(seed) & (2**64 - 1))
+        h = _vp()
+        op, mo = MadsOpts(pvars), make_motion(motion) if motion is not None else None
+        mesh = MadsMesh(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), 0) if g is not None else None
+        cs = make_cons(cons)
+        _check(self._L.mac_mads_begin_prog(
+            ctx._h, _ptr(x), x.size, _ptr(rm), float(penalty), _ptr(pv) if pv is not None else None,
+            _ptr(dl) if dl is not None else None, float(tan_half_fov), ctypes.byref(prm), lo, hi,
+            ctypes.byref(h), _opt(cs), ctypes.byref(op), _opt(mo), _opt(mesh), ctypes.byref(pg)))
+        self._h = h
+        self._done = _i32()
+
+    def poll(self, ahead: int = 0):
+        part = ProgPart()
+        _check(self._L.mac_mads_poll_prog(self._h, int(ahead), ctypes.byref(self._done), ctypes.byref(part)))
+        return bool(self._done.value), part
+
+    def advance(self, part):
+        """mac_mads_advance_prog: (outcome, chains): 'dominating' / 'improving' / 'unsuccessful', and
+        whether a record polled one iteration ahead applies next."""
+        if not isinstance(part, ProgPart):
+            part = ProgPart.from_words(part)
+        oc, ch = _i32(), _i32()
+        _check(self._L.mac_mads_advance_prog(self._h, ctypes.byref(part), ctypes.byref(oc), ctypes.byref(ch)))
+        return self.OUTCOMES[oc.value], bool(ch.value)
+
+    def result(self):
+        out = np.empty(self.n)
+        xi = np.full(self.n, np.nan)
+        st, ps = MadsStats(), MadsProgStats()
+        _check(self._L.mac_mads_result_prog(self._h, _ptr(out), _ptr(xi), ctypes.byref(st), ctypes.byref(ps)))
+        stats = {k: getattr(st, k) for k, _ in MadsStats._fields_}
+        stats.update({k: getattr(ps, k) for k, _ in MadsProgStats._fields_})
+        stats["x_infeasible"] = xi if ps.has_infeasible else None
+        return out, stats
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -22,6 +22,7 @@
 
 #include "k_common.h"
 #include "k_prep.h"
+#include "prog_rule.h"
 
 #pragma clang fp contract(off)
 
@@ -109,30 +110,7 @@ struct ProgSelArgs {
     double F_f, I_f, I_h, h_max;
 };
 
-// The 64-byte record the host reads once per iteration.
-struct ProgRec {
-    int64_t outcome;      // 0 dominating, 1 improving, 2 unsuccessful; bit 8: bestF replaces F
-    double bestF_f;       // the best feasible candidate (bestF_g < 0: none)
-    int64_t bestF_g;
-    double newI_f;        // the new infeasible incumbent (newI_g = -1: none, -2: the old one)
-    double newI_h;
-    int64_t newI_g;
-    double h_new;
-    int64_t evaluated;    // candidates with an objective other than +inf
-};
-static_assert(sizeof(ProgRec) == 64, "one 64-byte record");
-
-constexpr int64_t kProgNone = -1, kProgOld = -2;
-
-__device__ __forceinline__ bool prog_less2(double f, int64_t g, double f2, int64_t g2)
-{
-    return g >= 0 && (g2 < 0 || f < f2 || (f == f2 && g < g2));
-}
-
-__device__ __forceinline__ bool prog_less3(double f, double h, int64_t g, double f2, double h2, int64_t g2)
-{
-    return g >= 0 && (g2 < 0 || f < f2 || (f == f2 && (h < h2 || (h == h2 && g < g2))));
-}
+// (ProgRec, the 64-byte record the host reads once per iteration, and prog_less2 / prog_less3: prog_rule.h)
 
 __global__ __launch_bounds__(kProgSelBlock) void prog_select_kernel(uint64_t* ts, ProgSelArgs a,
                                                                   ProgRec* __restrict__ rec)
@@ -269,6 +247,73 @@ __global__ __launch_bounds__(kProgSelBlock) void prog_select_kernel(uint64_t* ts
         rec->newI_g = ng;
         rec->h_new = h_new;
         rec->evaluated = cnt;
+    }
+    ts_end(ts);
+}
+
+// ------------------------------------------------------------------ the barrier's update, one shard
+// The shard-partial record of prog_rule.h over one shard of an iteration's polls: per centre c the Kc
+// candidates lo .. lo + Kc - 1 of its K (objectives and h as the chain and prog_h_kernel left them for
+// the shard; null: the centre was not polled), global index g = c K + lo + k. One workgroup, one pass:
+// every thread folds its strided candidates (prog_part_fold), the waves merge by shuffles, the four
+// wave records meet in LDS and thread 0 writes the 96 bytes. Every field merges under a total order,
+// so the record does not depend on the order the lanes combine in. No atomics, no second pass.
+constexpr int kProgPartBlock = 256;
+
+struct ProgPartArgs {
+    const double* obj[2];
+    const double* h[2];
+    int Kc, K;
+    int64_t lo, tag;
+    ProgScalars s;
+};
+
+__device__ __forceinline__ ProgPart prog_part_shfl(const ProgPart& p, int off)
+{
+    ProgPart q;
+    q.tag = p.tag;
+    q.evaluated = __shfl_xor((long long)p.evaluated, off, kWave);
+    q.bestF_f = __shfl_xor(p.bestF_f, off, kWave);
+    q.bestF_g = __shfl_xor((long long)p.bestF_g, off, kWave);
+    q.dominates = __shfl_xor((int)p.dominates, off, kWave);
+    q.h_below = __shfl_xor(p.h_below, off, kWave);
+    q.keep_f = __shfl_xor(p.keep_f, off, kWave);
+    q.keep_h = __shfl_xor(p.keep_h, off, kWave);
+    q.keep_g = __shfl_xor((long long)p.keep_g, off, kWave);
+    q.drop_f = __shfl_xor(p.drop_f, off, kWave);
+    q.drop_h = __shfl_xor(p.drop_h, off, kWave);
+    q.drop_g = __shfl_xor((long long)p.drop_g, off, kWave);
+    return q;
+}
+
+__global__ __launch_bounds__(kProgPartBlock) void prog_part_kernel(uint64_t* ts, ProgPartArgs a,
+                                                                   ProgPart* __restrict__ out)
+{
+    constexpr int W = kProgPartBlock / kWave;
+    __shared__ ProgPart s_part[W];
+    ts_begin(ts);   // profiling only (k_common.h)
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    ProgPart p = prog_part_empty(a.tag);
+    const int64_t total = 2 * (int64_t)a.Kc;
+    for (int64_t e = tid; e < total; e += kProgPartBlock) {
+        const int c = e >= a.Kc ? 1 : 0;
+        if (!a.obj[c]) continue;
+        const int k = (int)(e - (int64_t)c * a.Kc);
+        const double f = a.obj[c][k];
+        if (f == __builtin_inf()) continue;   // (not evaluated: its h may never have been written)
+        prog_part_fold(p, a.s, f, a.h[c][k], (int64_t)c * a.K + a.lo + k);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const ProgPart q = prog_part_shfl(p, off);
+        prog_part_merge(p, q);
+    }
+    if (lane == 0) s_part[wave] = p;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 1; q < W; ++q) prog_part_merge(p, s_part[q]);
+        *out = p;
     }
     ts_end(ts);
 }

@@ -1,7 +1,8 @@
 // mads_driver.h — host only: the native MADS driver (mac_mads_begin* / _poll / _update / _poll_ahead /
-// _advance / _result, the pipelined mac_mads_run* and the progressive barrier's mac_mads_run_prog) on
+// _advance / _result, the pipelined mac_mads_run*, the progressive barrier's mac_mads_run_prog and its
+// stepper mac_mads_begin_prog / _poll_prog / _advance_prog / _result_prog with mac_prog_merge) on
 // mads_walk.h's arithmetic. Included once by maxcover.hip, after everything the driver calls
-// (enqueue_eval, the lanes, the constraint uploads, prog_select_launch).
+// (enqueue_eval, the lanes, the constraint uploads, prog_select_launch, prog_part_launch).
 #pragma once
 
 #include "mads_walk.h"
@@ -14,6 +15,7 @@ extern "C" {
 // their local bests (16 B each, lexicographic (objective, index) minimum) and all apply the same
 // update, so they stay in lock step with the single-GPU loop (mac_mads_run = one stepper owning
 // the whole poll).
+struct MadsProg;   // the progressive barrier's state of a prog stepper (mac_mads_begin_prog, below)
 struct mac_mads {
     mac_ctx* ctx = nullptr;
     Lane* L = nullptr;
@@ -63,16 +65,42 @@ struct mac_mads {
     // rings
     DevBuf d_x, d_st, d_ring;
     PinnedBuf h_ring;
-    ~mac_mads()
-    {
-        d_x.release();
-        d_gran.release();
-        d_feas.release();
-        d_st.release();
-        d_ring.release();
-        h_ring.release();
-    }
+    MadsProg* pg = nullptr;       // a prog stepper: stepped by mac_mads_poll_prog / _advance_prog alone
+    ~mac_mads();
 };
+
+// An incumbent of the progressive barrier: F (h == 0) or I (0 < h <= h_max).
+struct ProgInc {
+    std::vector<double> x;
+    double f = INFINITY, h = 0.0;
+    bool has = false;
+};
+
+struct MadsProg {
+    ProgArgs pargs{};
+    ProgInc F, I;
+    double h_max = INFINITY;
+    int64_t n_dom = 0, n_imp = 0, n_uns = 0, two = 0, evaluated = 0;
+    // pinned staging: per centre [centre 8n][permutations 4*2np][h fill 8 Kc], then the record
+    PinnedBuf stage;
+    size_t stage_c = 0, stage_sz = 0;
+    ProgPart* h_part = nullptr;
+    char* d_xinc[2] = {nullptr, nullptr};
+    double* d_h[2] = {nullptr, nullptr};
+    ProgScalars scalars() const { return ProgScalars{F.has, I.has, F.f, I.f, I.h, h_max}; }
+    ~MadsProg() { stage.release(); }
+};
+
+inline mac_mads::~mac_mads()
+{
+    delete pg;
+    d_x.release();
+    d_gran.release();
+    d_feas.release();
+    d_st.release();
+    d_ring.release();
+    h_ring.release();
+}
 
 static double* mads_best_ptr(mac_mads* m) { return m->ext_best ? m->ext_best : m->L->best.as<double>(); }
 
@@ -479,6 +507,7 @@ int32_t mac_mads_poll(mac_mads* m, int32_t* done, double* best_obj, int64_t* bes
 {
     ABI_BEGIN
     if (!m || !done || !best_obj || !best_idx) return fail(MAC_E_INVAL, "null argument");
+    if (m->pg) return fail(MAC_E_INVAL, "mac_mads_poll on a prog stepper (use mac_mads_poll_prog)");
     if (m->polled_b) return fail(MAC_E_INVAL, "mac_mads_poll twice without mac_mads_update");
     *done = 0;
     if (m->it >= m->prm.n_iter || m->ell < 0) {
@@ -526,6 +555,7 @@ int32_t mac_mads_update(mac_mads* m, double best_obj, int64_t best_idx)
 {
     ABI_BEGIN
     if (!m) return fail(MAC_E_INVAL, "null stepper");
+    if (m->pg) return fail(MAC_E_INVAL, "mac_mads_update on a prog stepper (use mac_mads_advance_prog)");
     if (!m->polled_b) return fail(MAC_E_INVAL, "mac_mads_update without a poll");
     if (best_idx >= m->K) return fail(MAC_E_INVAL, "best index outside the poll");
     const auto te0 = MadsClock::now();
@@ -552,6 +582,7 @@ int32_t mac_mads_poll_ahead(mac_mads* m, int32_t ahead, int32_t* done, double* b
     ABI_BEGIN
     if (!m || !done || !best_obj || !best_idx) return fail(MAC_E_INVAL, "null argument");
     if (feasible) *feasible = 0;
+    if (m->pg) return fail(MAC_E_INVAL, "mac_mads_poll_ahead on a prog stepper (use mac_mads_poll_prog)");
     if (ahead < 0) return fail(MAC_E_INVAL, "negative ahead");
     if (m->polled_b) return fail(MAC_E_INVAL, "mac_mads_poll_ahead with a mac_mads_poll pending");
     *done = 0;
@@ -585,6 +616,7 @@ int32_t mac_mads_advance(mac_mads* m, double best_obj, int64_t best_idx, int32_t
 {
     ABI_BEGIN
     if (!m) return fail(MAC_E_INVAL, "null stepper");
+    if (m->pg) return fail(MAC_E_INVAL, "mac_mads_advance on a prog stepper (use mac_mads_advance_prog)");
     if (m->polled_b) return fail(MAC_E_INVAL, "mac_mads_advance with a mac_mads_poll pending (use mac_mads_update)");
     if (best_idx >= m->K) return fail(MAC_E_INVAL, "best index outside the poll");
     if (m->it >= m->prm.n_iter || m->ell < 0) return fail(MAC_E_INVAL, "mac_mads_advance past the loop's end");
@@ -637,6 +669,7 @@ int32_t mac_mads_best_buffer(mac_mads* m, void* d_best16)
 {
     ABI_BEGIN
     if (!m) return fail(MAC_E_INVAL, "null stepper");
+    if (m->pg) return fail(MAC_E_INVAL, "mac_mads_best_buffer on a prog stepper (its polls report a mac_prog_part)");
     if (((uintptr_t)d_best16 & 7) != 0) return fail(MAC_E_INVAL, "d_best16 not 8-byte aligned");
     m->ext_best = (double*)d_best16;
     if (d_best16 && m->hi == m->lo) {   // an empty shard never polls: it offers {+inf, -1}
@@ -1073,6 +1106,285 @@ int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const
     rc = mac_mads_result(m, nullptr, st);
     mac_mads_destroy(m);
     return rc;
+    ABI_END
+}
+
+// ------------------------------------------------------------------ the progressive barrier as a stepper
+// mac_mads_run_prog's loop one iteration at a time over the shard [lo, hi) of every centre's poll
+// (mac_mads_begin_prog / _poll_prog / _advance_prog / _result_prog): a poll reports the shard-partial
+// record of prog_rule.h (prog_part_kernel, one pass), the ranks merge their records (mac_prog_merge: exact,
+// in any order) and all apply the merged one, so they hold the single-GPU loop's F, I and h_max. A poll
+// `ahead` iterations on assumes that the iterations between are unsuccessful and leave I as it is
+// (prog_chains): the same centres, ell - ahead, the threshold such an iteration leaves.
+static_assert(sizeof(mac_prog_part) == sizeof(ProgPart), "mac_prog_part is ProgPart");
+
+int32_t mac_mads_begin_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const double* r_max, double penalty,
+                            const double* prev, const double* d_lim, double tan_half_fov,
+                            const mac_mads_params* prm, int64_t shard_lo, int64_t shard_hi, mac_mads** out,
+                            const mac_cons* cons, const mac_mads_opts* opts, const mac_motion* motion,
+                            const mac_mads_mesh* mesh, const mac_prog* prog)
+{
+    ABI_BEGIN
+    if (out) *out = nullptr;
+    bool on = false;
+    int32_t rc = prog_check(prog, three_n, &on);
+    if (rc) return rc;
+    MadsSetup su{cons, opts, motion, mesh};
+    if (!on)   // no progressive constraint: the _mesh call
+        return mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi,
+                               out, su);
+    if (!x0 || !out) return fail(MAC_E_INVAL, "null argument");
+    const int N = (int)(three_n / 3);
+    const double h0 = prog_h_host(x0, N, prog);
+    if (h0 != h0) return fail(MAC_E_INVAL, "mac_prog: h(x0) is NaN");
+    const bool given = prog->h_max0 >= 0.0;   // (NaN: false)
+    const double h_max = given ? prog->h_max0 : (h0 > 0.0 ? h0 : (double)INFINITY);
+    if (h0 > h_max)
+        return fail(MAC_E_INVAL, "mac_prog: h(x0) = " + std::to_string(h0) + " > h_max0 = " + std::to_string(h_max));
+    rc = mads_setup_check(su, three_n);
+    if (rc) return rc;
+    mac_mads* m = nullptr;
+    rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi, &m, su);
+    if (rc) return rc;
+    try {
+        set_device(ctx);
+        Lane* L = m->L;
+        const size_t Kc = (size_t)(m->hi - m->lo);
+        MadsProg* pg = m->pg = new MadsProg();
+        pg->pargs = prog_upload(L, m->s, N, prog);
+        HCK(hipStreamSynchronize(m->s));   // (the caller's arrays may go once the call returns)
+        L->progh.reserve(sizeof(double) * 2 * std::max<size_t>(Kc, 1));
+        L->progobj.reserve(sizeof(double) * std::max<size_t>(Kc, 1));
+        L->progrec.reserve(sizeof(ProgPart));
+        pg->d_h[0] = L->progh.as<double>();
+        pg->d_h[1] = L->progh.as<double>() + Kc;
+        pg->stage_c = sizeof(double) * (size_t)m->n + sizeof(int) * 2 * (size_t)m->np;
+        pg->stage_sz = ((pg->stage_c + 7) & ~(size_t)7) + sizeof(double) * Kc;
+        pg->stage.reserve(2 * pg->stage_sz + sizeof(ProgPart));
+        pg->h_part = reinterpret_cast<ProgPart*>((char*)pg->stage.p + 2 * pg->stage_sz);
+        const size_t xinc_c = (pg->stage_c + 255) & ~(size_t)255;   // a centre's xinc: the lane's buffer holds both
+        L->xinc.reserve(2 * xinc_c);
+        pg->d_xinc[0] = (char*)L->xinc.p;
+        pg->d_xinc[1] = (char*)L->xinc.p + xinc_c;
+        ProgInc& inc = h0 == 0.0 ? pg->F : pg->I;
+        inc.x = m->x;
+        inc.f = m->f;
+        inc.h = h0;
+        inc.has = true;
+        pg->h_max = h_max;
+    } catch (...) {
+        mac_mads_destroy(m);
+        throw;
+    }
+    *out = m;
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_mads_poll_prog(mac_mads* m, int32_t ahead, int32_t* done, mac_prog_part* part)
+{
+    ABI_BEGIN
+    if (!m || !done || !part) return fail(MAC_E_INVAL, "null argument");
+    if (!m->pg) return fail(MAC_E_INVAL, "mac_mads_poll_prog on a stepper without a prog (use mac_mads_poll)");
+    if (ahead < 0) return fail(MAC_E_INVAL, "negative ahead");
+    MadsProg* pg = m->pg;
+    *done = 0;
+    const int64_t tag = m->it + ahead + 1;
+    ProgPart pp = prog_part_empty(tag);
+    if (m->it + ahead >= m->prm.n_iter || m->ell - ahead < 0) {
+        *done = 1;
+        pp.tag |= kProgTagDone;
+        std::memcpy(part, &pp, sizeof(pp));
+        return MAC_OK;
+    }
+    const int Kc = (int)(m->hi - m->lo);
+    if (Kc == 0) {   // an empty shard: no launch, the empty record
+        std::memcpy(part, &pp, sizeof(pp));
+        return MAC_OK;
+    }
+    set_device(m->ctx);
+    mac_ctx* ctx = m->ctx;
+    Lane* L = m->L;
+    hipStream_t s = m->s;
+    const auto ta = MadsClock::now();
+    const int64_t b = (int64_t)1 << (m->ell - ahead);
+    const uint64_t state = m->stream.state_after((uint64_t)ahead);
+    std::vector<int> rp_a, cp_a;   // (ahead = 0: the current iteration's permutations are computed already)
+    if (ahead > 0) m->stream.draw(state, rp_a, cp_a);
+    const std::vector<int>& rp = ahead > 0 ? rp_a : m->rp_next;
+    const std::vector<int>& cp = ahead > 0 ? cp_a : m->cp_next;
+    // what an unsuccessful iteration leaves: h_max = I.h with an I, else as it was
+    ProgScalars sc = pg->scalars();
+    if (ahead > 0 && pg->I.has) sc.h_max = pg->I.h;
+    const ProgInc* cen[2] = {nullptr, nullptr};
+    int nc = 0;
+    if (pg->F.has) cen[nc++] = &pg->F;
+    if (pg->I.has) cen[nc++] = &pg->I;
+    const double* sel_obj[2] = {nullptr, nullptr};   // (a centre cons3 rejected whole stays null)
+    const double* sel_h[2] = {nullptr, nullptr};
+    bool any = false;
+    for (int c = 0; c < nc; ++c) {
+        if (poll_rejected(m, b, cen[c]->x.data())) continue;   // (counted by mac_mads_advance_prog once applied)
+        char* hs = (char*)pg->stage.p + (size_t)c * pg->stage_sz;
+        const int* d_perm = mads_stage(m, cen[c]->x.data(), rp, cp, hs, pg->d_xinc[c]);
+        const CandSrc src = mads_gen_src(m, reinterpret_cast<const double*>(pg->d_xinc[c]), d_perm, state, b, (int)m->lo);
+        ProgLaunch pl{pg->pargs, sc.h_max, pg->d_h[c]};
+        if (m->xy) {   // the radii are held: every candidate's h is the centre's (<= h_max)
+            double* hh = reinterpret_cast<double*>(hs + ((pg->stage_c + 7) & ~(size_t)7));
+            std::fill(hh, hh + Kc, cen[c]->h);
+            HCK(hipMemcpyAsync(pg->d_h[c], hh, sizeof(double) * (size_t)Kc, hipMemcpyHostToDevice, s));
+        }
+        EvalReq rq = mads_request(m, src, Kc);
+        rq.d_feas = m->d_feas.as<unsigned long long>();
+        rq.prog = m->xy ? nullptr : &pl;
+        enqueue_eval(ctx, L, s, rq);
+        sel_h[c] = pg->d_h[c];
+        if (c == 0 && nc == 2) {
+            HCK(hipMemcpyAsync(L->progobj.p, L->obj.p, sizeof(double) * (size_t)Kc, hipMemcpyDeviceToDevice, s));
+            sel_obj[c] = L->progobj.as<double>();
+        } else {
+            sel_obj[c] = L->obj.as<double>();
+        }
+        any = true;
+    }
+    const auto tb = MadsClock::now();
+    if (any) {
+        prog_part_launch(s, prog_take_ts(ctx, kRoleProgSel, 1), sel_obj, sel_h, Kc, m->K, m->lo, tag, sc,
+                         L->progrec.as<ProgPart>());
+        HCK(hipMemcpyAsync(pg->h_part, L->progrec.p, sizeof(ProgPart), hipMemcpyDeviceToHost, s));
+        HCK(hipStreamSynchronize(s));
+        pp = *pg->h_part;
+    }
+    std::memcpy(part, &pp, sizeof(pp));
+    m->h_enq += mads_secs(ta, tb);
+    m->h_wait += mads_secs(tb, MadsClock::now());
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_prog_merge(const mac_prog_part* parts, int32_t n, mac_prog_part* out)
+{
+    ABI_BEGIN
+    if (!parts || !out) return fail(MAC_E_INVAL, "null argument");
+    if (n < 1) return fail(MAC_E_INVAL, "mac_prog_merge: no record");
+    ProgPart acc;
+    std::memcpy(&acc, &parts[0], sizeof(acc));
+    for (int32_t q = 1; q < n; ++q) {
+        ProgPart p;
+        std::memcpy(&p, &parts[q], sizeof(p));
+        if (p.tag != acc.tag)
+            return fail(MAC_E_INVAL, "mac_prog_merge: records of different iterations (tags " +
+                                         std::to_string(acc.tag) + " and " + std::to_string(p.tag) + ")");
+        prog_part_merge(acc, p);
+    }
+    std::memcpy(out, &acc, sizeof(acc));
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_mads_advance_prog(mac_mads* m, const mac_prog_part* merged, int32_t* outcome, int32_t* chains)
+{
+    ABI_BEGIN
+    if (!m || !merged) return fail(MAC_E_INVAL, "null argument");
+    if (!m->pg) return fail(MAC_E_INVAL, "mac_mads_advance_prog on a stepper without a prog (use mac_mads_advance)");
+    if (m->it >= m->prm.n_iter || m->ell < 0) return fail(MAC_E_INVAL, "mac_mads_advance_prog past the loop's end");
+    MadsProg* pg = m->pg;
+    ProgPart pp;
+    std::memcpy(&pp, merged, sizeof(pp));
+    if (pp.tag != m->it + 1)
+        return fail(MAC_E_INVAL, "mac_mads_advance_prog: the record's tag " + std::to_string(pp.tag) +
+                                     " is not iteration " + std::to_string(m->it + 1));
+    const auto t0 = MadsClock::now();
+    const int n = m->n, K = m->K;
+    const int64_t b = (int64_t)1 << m->ell;
+    const ProgInc* cen[2] = {nullptr, nullptr};
+    int nc = 0;
+    if (pg->F.has) cen[nc++] = &pg->F;
+    if (pg->I.has) cen[nc++] = &pg->I;
+    const bool had_I = pg->I.has;
+    const ProgRec r = prog_finish(pp, pg->scalars());
+    const bool improves = (r.outcome & 256) != 0;
+    const int64_t top = (int64_t)nc * K;
+    if ((improves && r.bestF_g >= top) || r.newI_g >= top)
+        return fail(MAC_E_INVAL, "mac_mads_advance_prog: a candidate index outside the polls");
+    ++m->it;
+    if (nc == 2) ++pg->two;
+    for (int c = 0; c < nc; ++c) {
+        m->evals += K;
+        // the applied poll's whole-poll rejection, decided as mac_mads_poll_prog does
+        if (m->hi > m->lo && poll_rejected(m, b, cen[c]->x.data())) ++m->rejected;
+    }
+    // candidate g = c K + k of this iteration: centre c moved along column k of the basis
+    // (the current iteration's permutations: rp_next / cp_next)
+    auto point = [&](int64_t g, std::vector<double>& out) {
+        out.resize(n);
+        mads_candidate(mads_poll_at(m, b, m->rp_next, m->cp_next), g % K, cen[g / K]->x.data(), n, out.data());
+    };
+    std::vector<double> xF, xI;
+    if (improves) point(r.bestF_g, xF);
+    if (r.newI_g >= 0) point(r.newI_g, xI);
+    if (improves) {
+        pg->F.x.swap(xF);
+        pg->F.f = r.bestF_f;
+        pg->F.has = true;
+    }
+    if (r.newI_g >= 0) {
+        pg->I.x.swap(xI);
+        pg->I.f = r.newI_f;
+        pg->I.h = r.newI_h;
+        pg->I.has = true;
+    } else if (r.newI_g == kProgNone) {
+        pg->I.has = false;
+    }
+    pg->h_max = r.h_new;
+    pg->evaluated += r.evaluated;
+    switch ((int)(r.outcome & 255)) {
+    case 0:
+        m->ell = std::min(m->ell + 1, (int)m->prm.ell_max);
+        ++pg->n_dom;
+        ++m->succ;
+        break;
+    case 1:
+        ++pg->n_imp;
+        break;
+    default:
+        --m->ell;
+        ++pg->n_uns;
+    }
+    m->stream.advance();
+    if (m->it < m->prm.n_iter) m->stream.draw(m->stream.state, m->rp_next, m->cp_next);
+    if (outcome) *outcome = (int32_t)(r.outcome & 255);
+    if (chains) *chains = prog_chains(r, had_I) ? 1 : 0;
+    m->h_post += mads_secs(t0, MadsClock::now());
+    return MAC_OK;
+    ABI_END
+}
+
+int32_t mac_mads_result_prog(mac_mads* m, double* x_out, double* x_inf_out, mac_mads_stats* st,
+                             mac_mads_prog_stats* ps)
+{
+    ABI_BEGIN
+    if (!m) return fail(MAC_E_INVAL, "null stepper");
+    if (!m->pg) return fail(MAC_E_INVAL, "mac_mads_result_prog on a stepper without a prog (use mac_mads_result)");
+    const MadsProg* pg = m->pg;
+    const ProgInc& out = pg->F.has ? pg->F : pg->I;
+    m->x = out.x;
+    m->f = out.f;
+    if (x_inf_out && pg->I.has) std::copy(pg->I.x.begin(), pg->I.x.end(), x_inf_out);
+    if (ps) {
+        ps->has_feasible = pg->F.has ? 1 : 0;
+        ps->has_infeasible = pg->I.has ? 1 : 0;
+        ps->f_feasible = pg->F.has ? pg->F.f : INFINITY;
+        ps->f_infeasible = pg->I.has ? pg->I.f : INFINITY;
+        ps->h_infeasible = pg->I.has ? pg->I.h : 0.0;
+        ps->h_max = pg->h_max;
+        ps->dominating = pg->n_dom;
+        ps->improving = pg->n_imp;
+        ps->unsuccessful = pg->n_uns;
+        ps->two_centre_polls = pg->two;
+        ps->evaluated = pg->evaluated;
+    }
+    return mac_mads_result(m, x_out, st);
     ABI_END
 }
 

@@ -4043,6 +4043,73 @@ int32_t mac_diag_prog_select(mac_ctx* ctx, const double* obj0, const double* h0,
     ABI_END
 }
 
+// prog_part_kernel's launch: one workgroup over a shard's (objective, h) arrays of up to two centres, Kc
+// device doubles each (a centre that was not polled: null), the shard's first candidate lo of the poll's
+// K, the scalars by value, the 96-byte record into d_part. mac_mads_poll_prog and mac_diag_prog_part both
+// launch through here.
+static void prog_part_launch(hipStream_t s, uint64_t* ts, const double* const obj[2], const double* const h[2],
+                             int Kc, int K, int64_t lo, int64_t tag, const ProgScalars& sc, ProgPart* d_part)
+{
+    ProgPartArgs pa{};
+    for (int c = 0; c < 2; ++c) {
+        pa.obj[c] = obj[c];
+        pa.h[c] = h[c];
+    }
+    pa.Kc = Kc;
+    pa.K = K;
+    pa.lo = lo;
+    pa.tag = tag;
+    pa.s = sc;
+    hipLaunchKernelGGL(prog_part_kernel, dim3(1), dim3(kProgPartBlock), 0, s, ts, pa, d_part);
+    HCK(hipGetLastError());
+}
+
+// host only, every build (not declared in maxcover.h): prog_part_kernel on given arrays, through the
+// stepper's own launch. Centre c: Kc host doubles of objectives and of h (the shard [lo, lo + Kc) of the
+// centre's K candidates), or both null; part12: the 96-byte ProgPart as the kernel wrote it.
+int32_t mac_diag_prog_part(mac_ctx* ctx, const double* obj0, const double* h0, const double* obj1,
+                           const double* h1, int64_t Kc, int64_t K, int64_t lo, int64_t tag, int32_t has_F,
+                           int32_t has_I, double F_f, double I_f, double I_h, double h_max, int64_t* part12)
+{
+    ABI_BEGIN
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    if (!part12) return fail(MAC_E_INVAL, "null record");
+    if (K < 1 || K > kProgSelDiagMaxK || Kc < 1 || lo < 0 || lo + Kc > K)
+        return fail(MAC_E_INVAL, "mac_diag_prog_part: need 1 <= Kc, 0 <= lo, lo + Kc <= K <= " +
+                                     std::to_string(kProgSelDiagMaxK));
+    if ((obj0 == nullptr) != (h0 == nullptr) || (obj1 == nullptr) != (h1 == nullptr))
+        return fail(MAC_E_INVAL, "mac_diag_prog_part: a centre's objectives given without its h, or its h alone");
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t kb = sizeof(double) * (size_t)Kc;
+    L->progobj.reserve(2 * kb);
+    L->progh.reserve(2 * kb);
+    L->progrec.reserve(sizeof(ProgPart));
+    const double* src_obj[2] = {obj0, obj1};
+    const double* src_h[2] = {h0, h1};
+    const double* d_obj[2] = {nullptr, nullptr};
+    const double* d_h[2] = {nullptr, nullptr};
+    for (int c = 0; c < 2; ++c) {
+        if (!src_obj[c]) continue;
+        double* po = L->progobj.as<double>() + (size_t)c * (size_t)Kc;
+        double* ph = L->progh.as<double>() + (size_t)c * (size_t)Kc;
+        HCK(hipMemcpyAsync(po, src_obj[c], kb, hipMemcpyHostToDevice, s));
+        HCK(hipMemcpyAsync(ph, src_h[c], kb, hipMemcpyHostToDevice, s));
+        d_obj[c] = po;
+        d_h[c] = ph;
+    }
+    const ProgScalars sc{has_F != 0, has_I != 0, F_f, I_f, I_h, h_max};
+    prog_part_launch(s, nullptr, d_obj, d_h, (int)Kc, (int)K, lo, tag, sc, L->progrec.as<ProgPart>());
+    ProgPart r;
+    HCK(hipMemcpyAsync(&r, L->progrec.p, sizeof(ProgPart), hipMemcpyDeviceToHost, s));
+    HCK(hipStreamSynchronize(s));
+    std::memcpy(part12, &r, sizeof(ProgPart));
+    return MAC_OK;
+    ABI_END
+}
+
 }  // extern "C" (mads_driver.h opens its own)
 
 // (host only, this file's own: the native MADS driver, on everything above)

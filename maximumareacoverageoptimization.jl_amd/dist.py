@@ -465,3 +465,136 @@ def mads_loop(stepper, gather=None):
             obj, idx = gather(obj, idx)
         stepper.update(obj, idx)
     return stepper.result()
+
+
+# ---------------------------------------------------------------- the progressive barrier's loops
+# A prog stepper (Context.mads_prog_stepper, or its host mirror TDM_STATIC_opt.ProgPollStepper) reports a
+# 96-byte shard-partial record per poll (mac_prog_part, include/maxcover.h): twelve
+# 8-byte words, exchanged as 12 float64 by their bits.
+
+def _part_words(part) -> np.ndarray:
+    """A record (a _lib.ProgPart or the mirrors' 12-tuple) as 12 float64 words."""
+    if hasattr(part, "words"):
+        return part.words()
+    from ._lib import ProgPart
+    return ProgPart(*part).words()
+
+
+def _part_like(words, like):
+    """12 words back into the form ``like`` has (a ProgPart, or the mirrors' tuple)."""
+    from ._lib import ProgPart
+    p = ProgPart.from_words(words)
+    return p if hasattr(like, "words") else p.as_tuple()
+
+
+def _merge_parts(parts):
+    """The records of one iteration merged: mac_prog_merge for ProgParts, the Python mirror for tuples."""
+    if hasattr(parts[0], "words"):
+        from ._lib import prog_merge
+        return prog_merge(parts)
+    from .TDM_STATIC_opt import prog_merge
+    return prog_merge(parts)
+
+
+class ProgGather:
+    """The prog loops' exchange: every rank's 96-byte record in rank order, one all-gather of 12 float64
+    per rank (RCCL on a GPU device, gloo on CPU) and one host read."""
+
+    def __init__(self, device="cpu", group=None):
+        import torch
+        import torch.distributed as dist
+
+        self.group = group
+        self.world = dist.get_world_size(group)
+        self.rank = dist.get_rank(group)
+        self.device = torch.device(device)
+        self.on_device = self.device.type == "cuda"
+        if self.on_device:
+            check_one_runtime()
+        self.stage = torch.zeros(12, dtype=torch.float64, pin_memory=self.on_device)
+        self.rec = torch.zeros(12, dtype=torch.float64, device=self.device)
+        self.out = torch.empty((self.world, 12), dtype=torch.float64, device=self.device)
+        self.host = (torch.empty((self.world, 12), dtype=torch.float64, pin_memory=True)
+                     if self.on_device else self.out)
+
+    def __call__(self, part):
+        import torch
+        import torch.distributed as dist
+
+        # (through int64: a copy of float64 values may quieten a signalling NaN pattern of an index word)
+        self.stage.view(torch.int64).copy_(torch.from_numpy(_part_words(part).view(np.int64)))
+        self.rec.view(torch.int64).copy_(self.stage.view(torch.int64))
+        dist.all_gather_into_tensor(self.out.view(torch.int64), self.rec.view(torch.int64).reshape(1, 12),
+                                    group=self.group)
+        if self.on_device:
+            self.host.view(torch.int64).copy_(self.out.view(torch.int64))
+        h = self.host.view(torch.int64).numpy().view(np.float64)
+        return [_part_like(h[j].copy(), part) for j in range(self.world)]
+
+
+class RcclProgGather:
+    """ProgGather's exchange inside libmaxcover (mac_exchange_records, up to 256 bytes per rank): the
+    record through the context's RCCL communicator in one C call."""
+
+    def __init__(self, ctx, device, group=None):
+        import torch
+
+        self.rank, self.world = _lib_comm(ctx, device, group)
+        self.ctx = ctx
+        self.rec = np.zeros(12, dtype=np.float64)
+        self.out = np.zeros((self.world, 12), dtype=np.float64)
+        self.stream = torch.cuda.Stream(torch.device(device))
+
+    def __call__(self, part):
+        self.rec.view(np.int64)[:] = _part_words(part).view(np.int64)
+        self.ctx.exchange_records(self.rec, self.out, stream=self.stream.cuda_stream)
+        return [_part_like(self.out[j].copy(), part) for j in range(self.world)]
+
+
+def mads_prog_loop(stepper, gather=None):
+    """The sharded loop under progressive constraints: per iteration the stepper polls its shard of every
+    centre's poll, ``gather`` (a ProgGather / RcclProgGather; None: one rank) collects the ranks' records,
+    every rank merges them (exact, in any order) and applies the merged one. The iterates are
+    Context.mads_run(prog=)'s. Returns stepper.result()."""
+    while True:
+        done, part = stepper.poll(0)
+        if done:
+            break
+        parts = gather(part) if gather is not None else [part]
+        stepper.advance(_merge_parts(parts))
+    return stepper.result()
+
+
+def mads_prog_loop_speculative(stepper, gather=None):
+    """The speculative loop under progressive constraints: rank j polls, with the whole poll, the
+    iteration that follows j iterations which are unsuccessful and leave I as it is (rank 0: the real
+    one); one exchange gathers the P records and every rank applies them in rank order until one is done
+    or does not chain. Unlike the plain loop's failures, an unsuccessful iteration may change I (no I
+    before, an infeasible candidate evaluated): such a one ends the round. The iterates are the
+    sequential loop's. Returns stepper.result() with ``rounds`` (exchanges) added to the statistics
+    (a dict's key, or the MADSResult's status attribute)."""
+    rank = gather.rank if gather is not None else 0
+    world = gather.world if gather is not None else 1
+    rounds = 0
+    finished = False
+    while not finished:
+        done, part = stepper.poll(rank)
+        recs = gather(part) if gather is not None else [part]
+        rounds += 1
+        for j in range(world):
+            p = recs[j]
+            tag = p.tag if hasattr(p, "tag") else p[0]
+            if tag & (1 << 62):
+                finished = True
+                break
+            _, chains = stepper.advance(p)
+            if not chains:
+                break
+    res = stepper.result()
+    if isinstance(res, tuple):
+        x, st = res
+        st = dict(st)
+        st["rounds"] = rounds
+        return x, st
+    res.status.rounds = rounds
+    return res
