@@ -70,6 +70,11 @@ extern "C" {
                                    (NULL, or every granularity 1.0) the option changes nothing. Results are
                                    the same under both; only the speed differs.        */
 
+#define MAC_OPT_VERDICTS     8  /* 0 (default) | 1: the native MADS driver tallies what rejected the candidates of
+                                   every poll it generates (mac_verdict_read, below). Read when a run or a
+                                   stepper begins, as MAC_OPT_MESH_KEYS is; a stepper keeps what it began with.
+                                   Results, statistics and the profiled launches are the same under both.       */
+
 #define MAC_KEYS_VALUE   0  /* offsets in metres from candidate 0's disk: exact at any granularity, packed
                                (fast) at integer granularities only                                          */
 #define MAC_KEYS_MESH    1  /* the poll's signed integer draws, base the incumbent, scale the disk's
@@ -341,6 +346,67 @@ int32_t mac_poll_best_motion_f64(mac_ctx* ctx, const double* cands, int64_t thre
 /* cons6's thresholds for one UAV: |fl(sqrt q3) - speed_prev| > a_max  <=>  q3 > *q_hi || q3 <= *q_lo
  * for every double q3 >= 0 (+inf / -1: that side never rejects). Host arithmetic only; no context. */
 void mac_motion_thresholds(double speed_prev, double a_max, double* q_hi, double* q_lo);
+
+/* ---- constraint verdicts: what rejected a candidate ---------------------------------------- */
+/* The calls above answer with one feasibility byte, one +inf objective or one count per candidate.
+ * A verdict says which constraints reject it, and on which UAVs. Every constraint that is ON is
+ * evaluated for every candidate: nothing is short-circuited, neither between constraints nor inside
+ * cons8's pair sweep. The defining identity: bit q of `reasons` is set exactly when the existing code
+ * rejects the candidate under that constraint alone, i.e. mac_cons_mask_motion_f64 with only that
+ * constraint on (kinds 1-5), or the +inf mac_poll_best_f64 reports under prev / d_lim (kind 0). The
+ * arithmetic is theirs (fp64, no FMA): cons3's 3-D move against dlim_threshold, cons7's and the
+ * motion constraints' per-UAV tests, cons8's pair predicate fl(fl(dx*dx)+fl(dy*dy)) <= T(d_sep) under
+ * the same sort and cull (a culled pair is proven feasible, so the pair count is exact). Non-finite
+ * inputs behave as in the masks: a UAV with a non-finite x or y is in no pair, a NaN operand rejects
+ * nothing. A kind that is OFF has its bit clear, its counts 0 and first_uav = -1; off means
+ * prev == NULL (cons3), d_sep <= 0 or NaN (cons8), a NULL descriptor (what it carries), else a NaN
+ * scalar or a NULL array exactly as the mask calls decide. All values are integers: they do not
+ * depend on thread order. */
+#define MAC_VERDICT_KINDS 6
+#define MAC_REJ_CONS3 0x01u   /* kind 0: src/TDM_Constraints.jl:54-75  (prev, d_lim)      */
+#define MAC_REJ_CONS8 0x02u   /* kind 1: :157-172  spacing    (mac_cons.d_sep)            */
+#define MAC_REJ_CONS7 0x04u   /* kind 2: :142-154  zone       (mac_cons.zone_y / zone_r)  */
+#define MAC_REJ_CONS4 0x08u   /* kind 3: :78-103   cone       (mac_motion.cone_cos)       */
+#define MAC_REJ_CONS5 0x10u   /* kind 4: :106-119  speed      (mac_motion.v_max)          */
+#define MAC_REJ_CONS6 0x20u   /* kind 5: :122-138  accel      (mac_motion.a_max)          */
+typedef struct mac_verdict {          /* 64 B per candidate */
+    uint32_t reasons;                 /* OR of MAC_REJ_* over the constraints that are ON and reject     */
+    int32_t  pairs;                   /* cons8: unordered pairs i<j that violate the spacing; 0 when off */
+    int32_t  n_uav[MAC_VERDICT_KINDS];     /* per kind: UAVs that violate it (cons8: UAVs in >= 1 such pair) */
+    int32_t  first_uav[MAC_VERDICT_KINDS]; /* per kind: the lowest such UAV index, -1 when none            */
+    int32_t  reserved[2];             /* written 0 */
+} mac_verdict;
+
+/* The verdicts of the K candidates of a 3N x K matrix (column-major, as every batch call takes it),
+ * one record each into out. Host pointers, fp64, synchronous; no point list is needed; K = 0 writes
+ * nothing. prev / d_lim / tan_half_fov are cons3's inputs as mac_poll_best_f64 takes them. Errors,
+ * before anything is launched: a null ctx, or a null out with K > 0: MAC_E_INVAL; three_n % 3 != 0:
+ * MAC_E_SIZE; N > 2048: MAC_E_INVAL; prev without d_lim: MAC_E_INVAL. May be called concurrently
+ * with evaluations, as mac_cons_mask_f64 may. */
+int32_t mac_cons_explain_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K,
+                             const double* prev, const double* d_lim, double tan_half_fov,
+                             const mac_cons* cons, const mac_motion* motion, mac_verdict* out);
+
+/* The native MADS driver's tally (MAC_OPT_VERDICTS = 1 when the run or stepper began, and cons3, a
+ * mac_cons or a mac_motion constraint on): every poll the driver generates (mac_mads_run*'s loop,
+ * mac_mads_poll, mac_mads_poll_ahead) enqueues one more launch over its shard, on the poll's stream
+ * behind its first launch; it writes scratch of its own and this tally, and nothing of the poll reads
+ * it. candidates: candidates examined; rejected_any: those with a non-zero `reasons`;
+ * rejected_by[q]: those with bit q set; polls: tallied launches (one per stepper and poll: two
+ * steppers that share a poll count it twice). A poll that cons3 rejects whole (rejected_polls) is not
+ * launched and not tallied, and neither is a poll the pipelined loop enqueued past its stop; polls
+ * ahead are tallied, as feasible_evaluations counts them. Without a mac_prog and with N <= 512,
+ * candidates - rejected_any of one stepper's polls is its feasible_evaluations. A run or stepper
+ * with a mac_prog ignores the option: the barrier's rejections are visible through mac_prog_h_f64 and
+ * mac_mads_prog_stats already (nothing is allocated or checked for it). With the option on and a
+ * constraint on (cons3 alone included), a run or stepper over N > 2048 UAVs is MAC_E_INVAL when it
+ * begins: the verdict launch sorts in LDS as the mask launch does. The launch stands behind the poll's
+ * first (prep) launch, because in the pipelined loop the prep decides the whole-poll rejection. The tally belongs to the context and adds up over its runs and
+ * steppers (integer adds: the same totals in any order). The call synchronises the device and
+ * copies the tally; every output may be NULL; reset != 0 zeroes it. With the option never set it
+ * reports zeros and touches no device. */
+int32_t mac_verdict_read(mac_ctx* ctx, int64_t* candidates, int64_t* rejected_any,
+                         int64_t* rejected_by /* MAC_VERDICT_KINDS */, int64_t* polls, int32_t reset);
 
 /* ---- native MADS driver ------------------------------------------ */
 /* A granular MADS with a complete LTMADS poll, the restatement of DirectSearch's Optimize!

@@ -10,8 +10,9 @@ Gabisanth/MaximumAreaCoverageOptimization.jl. Drop-in replacements for the hot p
 Plain `ccall` over the C ABI: no Julia package dependencies. The library path comes from
 ENV["MAXCOVER_LIB"] or defaults to the in-tree build. Not executed in this repository's CI
 (Julia is not installed in the build image) — the swarm-constraint wrappers (MacCons, cons_mask,
-poll_best's `cons`) and the high-interest region wrappers (set_regions!, regions_ingested,
-region_stats, percentage_covered) included; the ctypes mirror
+poll_best's `cons`), the verdict wrappers (MacVerdict, cons_explain, set_verdicts!, verdict_read)
+and the high-interest region wrappers (set_regions!, regions_ingested, region_stats,
+percentage_covered) included; the ctypes mirror
 (maximumareacoverageoptimization.jl_amd/_lib.py) makes the same calls with the same arrays and
 is what the parity tests exercise. See INTEGRATION.md.
 =#
@@ -20,7 +21,8 @@ module MaxCoverAMD
 export MacContext, set_points!, calculateArea, createObjective, objective_batch, poll_best,
        poll_basis, rmvCoveredPOI!, area_batch, area_by_disk, mads_run, MadsOpts, MacMadsMesh, MacProg, MadsProgStats, MacProgPart, MadsProgStepper,
        mads_prog_stepper, poll_prog!, advance_prog!, prog_merge, result_prog, close_prog!, MacCons, MacMotion, cons_mask,
-       set_mesh_keys!, set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
+       set_mesh_keys!, MacVerdict, cons_explain, set_verdicts!, verdict_read,
+       set_regions!, clear_regions!, regions_ingested, region_stats, percentage_covered
 
 const libmaxcover = get(ENV, "MAXCOVER_LIB",
     joinpath(@__DIR__, "..", "maximumareacoverageoptimization.jl_amd", "libmaxcover.so"))
@@ -276,6 +278,75 @@ function cons_mask(cands::Matrix{Float64}, cons::MacCons, ctx::MacContext)
                 (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ref{MacCons}, Ptr{UInt8}),
                 ctx, cands, size(cands, 1), K, Ref(cons), out))
     return out .!= 0x00
+end
+
+"""
+MacVerdict — mac_verdict (include/maxcover.h), the same 64 bytes: what rejected one candidate. `reasons`:
+the OR of the kinds' bits (cons3 0x01, cons8 0x02, cons7 0x04, cons4 0x08, cons5 0x10, cons6 0x20) over the
+constraints that are on and reject it; `pairs`: cons8's violating unordered pairs; `n_uav[q]` /
+`first_uav[q]` (kind q + 1 here: Julia tuples are 1-based; the UAV index itself stays 0-based, -1 = none):
+the UAVs whose own test fails and the lowest of them. Written against the header and, like the rest of
+this shim, never executed here.
+"""
+struct MacVerdict
+    reasons::UInt32
+    pairs::Int32
+    n_uav::NTuple{6,Int32}
+    first_uav::NTuple{6,Int32}
+    reserved::NTuple{2,Int32}
+end
+const VERDICT_KINDS = (:cons3, :cons8, :cons7, :cons4, :cons5, :cons6)
+
+"""
+cons_explain(cands, ctx; cons, motion, prev, d_lim, tan_half_fov) — mac_cons_explain_f64: one MacVerdict
+per column of the 3N x K candidates. Every constraint that is on is evaluated for every candidate (no
+short-circuit); cons3 through `prev` / `d_lim` as poll_best takes them. Needs no point list.
+"""
+function cons_explain(cands::Matrix{Float64}, ctx::MacContext; cons::Union{Nothing,MacCons} = nothing,
+                      motion::Union{Nothing,MacMotion} = nothing,
+                      prev::Union{Nothing,Vector{Float64}} = nothing,
+                      d_lim::Union{Nothing,Vector{Float64}} = nothing, tan_half_fov::Float64 = 1.0)
+    K = size(cands, 2)
+    out = Vector{MacVerdict}(undef, K)
+    rcons = cons === nothing ? nothing : Ref(cons)
+    rmot = motion === nothing ? nothing : Ref(CMotion(motion))
+    GC.@preserve prev d_lim motion rcons rmot begin
+        check(ccall((:mac_cons_explain_f64, libmaxcover), Int32,
+                    (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Float64,
+                     Ptr{MacCons}, Ptr{CMotion}, Ptr{MacVerdict}),
+                    ctx, cands, size(cands, 1), K, _ptr_or_null(prev), _ptr_or_null(d_lim), tan_half_fov,
+                    rcons === nothing ? Ptr{MacCons}(C_NULL) : Base.unsafe_convert(Ptr{MacCons}, rcons),
+                    rmot === nothing ? Ptr{CMotion}(C_NULL) : Base.unsafe_convert(Ptr{CMotion}, rmot), out))
+    end
+    return out
+end
+
+const MAC_OPT_VERDICTS = Int32(8)
+
+"""
+    set_verdicts!(ctx, on)
+
+Whether `mads_run` tallies what rejected the candidates of the polls it generates (MAC_OPT_VERDICTS;
+`verdict_read`). Read when a run begins; results are the same either way; a run with a `MacProg` ignores it.
+"""
+function set_verdicts!(ctx::MacContext, on::Bool)
+    check(ccall((:mac_set_option, libmaxcover), Int32, (Ptr{Cvoid}, Int32, Int64), ctx,
+                MAC_OPT_VERDICTS, on ? 1 : 0))
+    return ctx
+end
+
+"""
+verdict_read(ctx; reset = true) — mac_verdict_read: (candidates, rejected_any, rejected_by, polls) since
+the last reset, `rejected_by` a NamedTuple over VERDICT_KINDS. Synchronises the device.
+"""
+function verdict_read(ctx::MacContext; reset::Bool = true)
+    c, a, p = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    by = zeros(Int64, 6)
+    check(ccall((:mac_verdict_read, libmaxcover), Int32,
+                (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ref{Int64}, Int32),
+                ctx, c, a, by, p, reset ? 1 : 0))
+    return (candidates = c[], rejected_any = a[], rejected_by = NamedTuple{VERDICT_KINDS}(Tuple(by)),
+            polls = p[])
 end
 
 """

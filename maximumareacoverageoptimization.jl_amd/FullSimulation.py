@@ -166,7 +166,14 @@ class Simulation:
     Each record then gains ``h`` (of the step's output), ``has_feasible`` and the counts
     ``dominating`` / ``improving`` / ``unsuccessful``. ``penalty``: the objective's weight on
     sum |R_i - r_max_i| (src/TDM_STATIC_opt.jl:97), 1e5 as in the reference; 0 leaves the altitude to
-    the progressive constraint alone."""
+    the progressive constraint alone.
+    ``verdicts``: True switches on the native driver's tally of what rejected the candidates it polled
+    (Context.set_verdicts) and reads and resets it once per step: each record gains ``rejected_by``
+    (candidates per constraint, {"cons3": .., "cons8": .., "cons7": .., "cons4": .., "cons5": .., "cons6": ..};
+    a candidate counts under every constraint that rejects it), ``rejected_any`` and
+    ``polled_candidates`` (this rank's polls; the start points are not polled). The MADS outputs and the
+    other fields are what they are without it; under ``cons_prog`` the driver ignores the option and the
+    counts stay 0. False (default): the records and calls are what they were."""
 
     def __init__(self, ctx: Context, starting_circles, *, fire: DynamicArea | None = None,
                  firepoints=None, initial_points=None, N_iter: int = N_iter, d_lim=None,
@@ -174,7 +181,8 @@ class Simulation:
                  shard=None, gather=None, speculate: bool | None = None, device=None,
                  attribution: bool = False, cons_ext=(), high_interest=None, w_high=None,
                  poll_vars: str = "xyr", motion=None, velocities=None, granularity=None,
-                 cons_prog=(), h_max0=None, penalty: float = 1e5, mesh_keys: bool = False):
+                 cons_prog=(), h_max0=None, penalty: float = 1e5, mesh_keys: bool = False,
+                 verdicts: bool = False):
         if poll_vars not in ("xyr", "xy", "auto"):
             raise ValueError(f"poll_vars must be 'xyr', 'xy' or 'auto', not {poll_vars!r}")
         self.poll_vars = poll_vars
@@ -183,6 +191,10 @@ class Simulation:
         self.mesh_keys = bool(mesh_keys)
         if self.mesh_keys:   # (Context.set_mesh_keys: read as each step's run begins)
             ctx.set_mesh_keys(True)
+        self.verdicts = bool(verdicts)
+        if self.verdicts:    # (Context.set_verdicts: read as each step's run begins; the tally starts at 0)
+            ctx.set_verdicts(True)
+            ctx.verdict_read(reset=True)
         self.high_interest = self._boxes(high_interest)
         if self.high_interest is None and w_high is not None:
             raise ValueError("w_high needs high_interest")
@@ -396,6 +408,11 @@ class Simulation:
             rec["has_feasible"] = bool(st["has_feasible"])
             for k in ("dominating", "improving", "unsuccessful"):
                 rec[k] = int(st[k])
+        if self.verdicts:   # what rejected the step's polled candidates (read and reset once per step)
+            v = ctx.verdict_read(reset=True)
+            rec["rejected_by"] = v["rejected_by"]
+            rec["rejected_any"] = v["rejected_any"]
+            rec["polled_candidates"] = v["candidates"]
         if self.attribution:   # on the step's (post-removal) list
             rec["owned"], rec["exclusive"], _ = ctx.area_by_disk(x_out)
         if self.high_interest is not None:   # :537-557, on the step's (post-removal) list

@@ -29,6 +29,13 @@ def cons1(x) -> bool:
     return True
 
 
+def _cons3_rejects(prev, t: float, dl, xx, N: int, i: int) -> bool:
+    """UAV i's own cons3 test (:61-70): its 3-D move from ``prev`` is longer than ``dl[i]``."""
+    x1, y1, z1 = float(prev[i]), float(prev[N + i]), float(prev[2 * N + i]) / t
+    x2, y2, z2 = float(xx[i]), float(xx[N + i]), float(xx[2 * N + i]) / t
+    return math.sqrt((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2)) > dl[i]
+
+
 def create_cons3(pre_optimized_circles_MADS, FOV: float, d_lim):
     """src/TDM_Constraints.jl:54-75. ``pre_optimized_circles_MADS``: list of Circle or [x;y;R]."""
     from .AreaCoverageCalculation import make_MADS
@@ -45,10 +52,7 @@ def create_cons3(pre_optimized_circles_MADS, FOV: float, d_lim):
         xx = np.asarray(x, dtype=np.float64)
         N = xx.size // 3
         for i in range(N):
-            x1, y1, z1 = float(prev[i]), float(prev[N + i]), float(prev[2 * N + i]) / t
-            x2, y2, z2 = float(xx[i]), float(xx[N + i]), float(xx[2 * N + i]) / t
-            if math.sqrt((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2)) \
-                    > dl[i]:
+            if _cons3_rejects(prev, t, dl, xx, N, i):
                 return False
         return True
 
@@ -56,6 +60,11 @@ def create_cons3(pre_optimized_circles_MADS, FOV: float, d_lim):
     cons3.d_lim = dl
     cons3.tan_half_fov = t
     return cons3
+
+
+def _cons7_rejects(y_lim: float, r_lim: float, xx, N: int, i: int) -> bool:
+    """UAV i's own cons7 test (:146-150): inside the zone and above its cap."""
+    return float(xx[i + N]) < y_lim and float(xx[i + 2 * N]) > r_lim
 
 
 def create_cons7(FOV: float, y_below: float = 200.0, h_above: float = 19.0):
@@ -69,13 +78,20 @@ def create_cons7(FOV: float, y_below: float = 200.0, h_above: float = 19.0):
         xx = np.asarray(x, dtype=np.float64)
         N = xx.size // 3
         for i in range(N):
-            if float(xx[i + N]) < y_lim:
-                if float(xx[i + 2 * N]) > r_lim:
-                    return False
+            if _cons7_rejects(y_lim, r_lim, xx, N, i):
+                return False
         return True
 
     cons7.mac_cons = {"zone_y": y_lim, "zone_r": r_lim}
     return cons7
+
+
+def _cons8_pair(d: float, xx, N: int, i: int, j: int) -> bool:
+    """cons8's test of the pair (i, j) (:162-166): closer than ``d`` horizontally."""
+    dx = float(xx[i]) - float(xx[j])
+    dy = float(xx[i + N]) - float(xx[j + N])
+    hor_separation = math.sqrt(dx * dx + dy * dy)
+    return hor_separation < d
 
 
 def create_cons8(d_sep: float = 15.0):
@@ -88,12 +104,8 @@ def create_cons8(d_sep: float = 15.0):
         N = xx.size // 3
         for i in range(N):
             for j in range(N):
-                if j != i:
-                    dx = float(xx[i]) - float(xx[j])
-                    dy = float(xx[i + N]) - float(xx[j + N])
-                    hor_separation = math.sqrt(dx * dx + dy * dy)
-                    if hor_separation < d:
-                        return False
+                if j != i and _cons8_pair(d, xx, N, i, j):
+                    return False
         return True
 
     cons8.mac_cons = {"d_sep": d}
@@ -130,6 +142,24 @@ def cone_cosine(ux: float, uy: float, tx: float, ty: float) -> float:
         return float(np.float64(ux * tx + uy * ty) / den)
 
 
+def _cons4_rejects(a, v, cc: float, xx, N: int, i: int) -> bool:
+    """UAV i's own cons4 test: its move leaves the cone around its velocity (NaN: feasible)."""
+    tx, ty, _, _ = _move(xx, a, N, i)
+    return cone_cosine(float(v[i]), float(v[N + i]), tx, ty) < cc
+
+
+def _cons5_rejects(a, vm: float, xx, N: int, i: int) -> bool:
+    """UAV i's own cons5 test: its 3-D move from the anchor is longer than v_max."""
+    _, _, tz, q2 = _move(xx, a, N, i)
+    return _sqrt(q2 + tz * tz) > vm
+
+
+def _cons6_rejects(a, sp, am: float, xx, N: int, i: int) -> bool:
+    """UAV i's own cons6 test: its speed differs from speed_prev[i] by more than a_max."""
+    _, _, tz, q2 = _move(xx, a, N, i)
+    return abs(_sqrt(q2 + tz * tz) - float(sp[i])) > am
+
+
 def create_cons4(velocities, anchor, cone_cos: float = -0.5):
     """src/TDM_Constraints.jl:78-103 (the target stays inside a cone around the UAV's xy velocity,
     "to reduce oscillatory target setting"). ``velocities``: [vx; vy] (2N values);
@@ -146,8 +176,7 @@ def create_cons4(velocities, anchor, cone_cos: float = -0.5):
     def cons4(x) -> bool:
         xx = np.asarray(x, dtype=np.float64)
         for i in range(N):
-            tx, ty, _, _ = _move(xx, a, N, i)
-            if cone_cosine(float(v[i]), float(v[N + i]), tx, ty) < cc:
+            if _cons4_rejects(a, v, cc, xx, N, i):
                 return False
         return True
 
@@ -165,8 +194,7 @@ def create_cons5(anchor, v_max: float = 2.0):
     def cons5(x) -> bool:
         xx = np.asarray(x, dtype=np.float64)
         for i in range(N):
-            _, _, tz, q2 = _move(xx, a, N, i)
-            if _sqrt(q2 + tz * tz) > vm:
+            if _cons5_rejects(a, vm, xx, N, i):
                 return False
         return True
 
@@ -188,8 +216,7 @@ def create_cons6(anchor, speed_prev, a_max: float = 1.0):
     def cons6(x) -> bool:
         xx = np.asarray(x, dtype=np.float64)
         for i in range(N):
-            _, _, tz, q2 = _move(xx, a, N, i)
-            if abs(_sqrt(q2 + tz * tz) - float(sp[i])) > am:
+            if _cons6_rejects(a, sp, am, xx, N, i):
                 return False
         return True
 
@@ -226,6 +253,108 @@ def merge_mac_cons(constraints):
         else:
             plain.append(c)
     return (merged or None), plain
+
+
+# ---- verdicts: what rejects a trial point (include/maxcover.h mac_verdict)
+
+VERDICT_KINDS = ("cons3", "cons8", "cons7", "cons4", "cons5", "cons6")   # kind q = bit q of reasons
+
+
+def _descriptors(given):
+    """(mac_cons dict or None, mac_motion dict or None, cons3 data or None) from None, a mapping
+    (the mac_cons / mac_motion fields themselves, or under "cons" / "motion"), or callables that carry
+    ``mac_cons`` / ``mac_motion`` data or create_cons3's ``prev`` / ``d_lim`` / ``tan_half_fov``."""
+    if given is None:
+        return None, None, None
+    if hasattr(given, "get"):
+        cons, motion = given.get("cons"), given.get("motion")
+        if cons is None and motion is None:
+            cons = {k: given[k] for k in ("d_sep", "zone_y", "zone_r") if given.get(k) is not None}
+            motion = {k: given[k] for k in ("anchor", "vel", "speed_prev", "cone_cos", "v_max", "a_max")
+                      if given.get(k) is not None}
+        return (cons or None), (motion or None), None
+    cs = list(given)
+    cons, rest = merge_mac_cons(cs)
+    motion, rest = merge_mac_motion(rest)
+    c3 = next((c for c in rest if hasattr(c, "prev") and hasattr(c, "d_lim")), None)
+    return cons, motion, c3
+
+
+def explain(x, constraints=None, prev=None, d_lim=None, FOV: float = math.pi / 2, tan_half_fov=None):
+    """What rejects the trial point ``x`` = [x; y; R]: one record of ``_lib.VERDICT_DTYPE``, the
+    documented meaning of the device's mac_verdict (Context.cons_explain gives the same record).
+
+    ``constraints``: the callables of this module (create_cons3 / 4 / 5 / 6 / 7 / 8; one of each
+    kind), or a mapping of mac_cons / mac_motion fields. cons3 may also be given as ``prev``, ``d_lim``
+    and ``FOV`` (or ``tan_half_fov`` itself). Every constraint that is on is evaluated in full, with
+    the per-UAV and per-pair tests the callables themselves apply; none short-circuits another:
+      reasons       bit q set iff kind q (VERDICT_KINDS) is on and rejects x, i.e. iff
+                    ``not create_consq(...)(x)``
+      n_uav[q]      the UAVs whose own test fails (cons8: the UAVs in at least one violating pair)
+      first_uav[q]  the lowest of them, -1 when none
+      pairs         cons8's unordered pairs i < j closer than d_sep
+    A kind that is off (no data; d_sep <= 0 or NaN; a NaN bound; a missing array) has its bit clear,
+    its counts 0 and first_uav -1. A UAV with a non-finite x or y is in no pair; a NaN operand
+    rejects nothing."""
+    from ._lib import VERDICT_DTYPE
+    xx = np.asarray(x, dtype=np.float64).ravel()
+    N = xx.size // 3
+    cons, motion, c3 = _descriptors(constraints)
+    bad = [[] for _ in VERDICT_KINDS]   # per kind: the UAVs whose own test fails, ascending
+    pairs = 0
+    nan = float("nan")
+    if c3 is not None and prev is None:
+        prev, d_lim, tan_half_fov = c3.prev, c3.d_lim, c3.tan_half_fov
+    if prev is not None:
+        if d_lim is None:
+            raise ValueError("prev given without d_lim")
+        pv = np.asarray(prev, dtype=np.float64).ravel()
+        dl = np.asarray(d_lim, dtype=np.float64).ravel()
+        t = math.tan(FOV / 2) if tan_half_fov is None else float(tan_half_fov)
+        bad[0] = [i for i in range(N) if _cons3_rejects(pv, t, dl, xx, N, i)]
+    if cons:
+        d = float(cons.get("d_sep", nan) if cons.get("d_sep") is not None else nan)
+        zy = float(cons.get("zone_y", nan) if cons.get("zone_y") is not None else nan)
+        zr = float(cons.get("zone_r", nan) if cons.get("zone_r") is not None else nan)
+        if d > 0.0 and N > 1:
+            # _cons8_pair's test, restated on purpose: a Python call per pair is 2 million calls at
+            # N = 2048. numpy's subtract, multiply, add and sqrt round each result as the float
+            # operations do (no FMA), so UAV i against every j is the same test (pinned against
+            # create_cons8 and a per-pair loop in tests/test_verdict_host.py). 256 rows at a time.
+            px, py = xx[:N], xx[N:2 * N]
+            for i0 in range(0, N, 256):
+                i1 = min(i0 + 256, N)
+                with np.errstate(all="ignore"):
+                    dx = px[i0:i1, None] - px[None, :]
+                    dy = py[i0:i1, None] - py[None, :]
+                    close = np.sqrt(dx * dx + dy * dy) < d
+                rows = np.arange(i0, i1)
+                close[rows - i0, rows] = False                      # j != i
+                pairs += int(np.count_nonzero(close & (np.arange(N)[None, :] > rows[:, None])))
+                bad[1] += [int(i) for i in i0 + np.flatnonzero(close.any(axis=1))]
+        if zy == zy and zr == zr:
+            bad[2] = [i for i in range(N) if _cons7_rejects(zy, zr, xx, N, i)]
+    if motion and motion.get("anchor") is not None:
+        a = _anchor(motion["anchor"])
+        v, sp = motion.get("vel"), motion.get("speed_prev")
+        cc, vm, am = (float(motion[k]) if motion.get(k) is not None else nan
+                      for k in ("cone_cos", "v_max", "a_max"))
+        if cc == cc and v is not None:
+            v = np.asarray(v, dtype=np.float64).ravel()
+            bad[3] = [i for i in range(N) if _cons4_rejects(a, v, cc, xx, N, i)]
+        if vm == vm:
+            bad[4] = [i for i in range(N) if _cons5_rejects(a, vm, xx, N, i)]
+        if am == am and sp is not None:
+            sp = np.asarray(sp, dtype=np.float64).ravel()
+            bad[5] = [i for i in range(N) if _cons6_rejects(a, sp, am, xx, N, i)]
+    rec = np.zeros((), dtype=VERDICT_DTYPE)
+    rec["pairs"] = pairs
+    for q, b in enumerate(bad):
+        rec["n_uav"][q] = len(b)
+        rec["first_uav"][q] = b[0] if b else -1
+        if b:
+            rec["reasons"] |= np.uint32(1 << q)
+    return rec
 
 
 # ---- progressive constraints (src/TDM_Constraints.jl:182-220): altitude excess, handed to MADS's

@@ -32,6 +32,7 @@ MAC_OPT_PROFILE = 4
 MAC_OPT_SHARED = 5
 MAC_OPT_CHAIN = 6
 MAC_OPT_MESH_KEYS = 7
+MAC_OPT_VERDICTS = 8
 MAC_KEYS_VALUE = 0
 MAC_KEYS_MESH = 1
 SHARED_MODES = {"auto": 0, "fp64": 1, "bits": 2}
@@ -89,6 +90,7 @@ EXPORTS = (
     "mac_prog_h_f64", "mac_mads_run_prog", "mac_diag_poll_report",
     "mac_mads_begin_prog", "mac_mads_poll_prog", "mac_prog_merge", "mac_mads_advance_prog",
     "mac_mads_result_prog",
+    "mac_cons_explain_f64", "mac_verdict_read",
 )
 
 MAC_REGIONS_MAX = 64
@@ -252,6 +254,27 @@ def make_motion(motion=None, anchor=None, vel=None, speed_prev=None, cone_cos: f
     m._keep = keep   # the arrays the pointers refer to
     m.n_uav = N
     return m
+
+
+MAC_VERDICT_KINDS = 6
+# kind q of a verdict, in bit order (MAC_REJ_CONS3 = 1 << 0, ...)
+VERDICT_KINDS = ("cons3", "cons8", "cons7", "cons4", "cons5", "cons6")
+MAC_REJ_CONS3, MAC_REJ_CONS8, MAC_REJ_CONS7 = 0x01, 0x02, 0x04
+MAC_REJ_CONS4, MAC_REJ_CONS5, MAC_REJ_CONS6 = 0x08, 0x10, 0x20
+
+
+class Verdict(ctypes.Structure):
+    """mac_verdict (include/maxcover.h): what rejected one candidate (64 B). reasons: the OR of
+    MAC_REJ_* over the constraints that are on and reject it; pairs: cons8's violating unordered
+    pairs; n_uav[q] / first_uav[q]: the UAVs that violate kind q and the lowest of them (-1: none)."""
+    _fields_ = [("reasons", ctypes.c_uint32), ("pairs", ctypes.c_int32),
+                ("n_uav", ctypes.c_int32 * MAC_VERDICT_KINDS),
+                ("first_uav", ctypes.c_int32 * MAC_VERDICT_KINDS), ("reserved", ctypes.c_int32 * 2)]
+
+
+# the same 64 bytes as a numpy record (Context.cons_explain's and TDM_Constraints.explain's result)
+VERDICT_DTYPE = np.dtype([("reasons", "<u4"), ("pairs", "<i4"), ("n_uav", "<i4", (MAC_VERDICT_KINDS,)),
+                          ("first_uav", "<i4", (MAC_VERDICT_KINDS,)), ("reserved", "<i4", (2,))])
 
 
 class Prog(ctypes.Structure):
@@ -446,6 +469,9 @@ def _declare(L: ctypes.CDLL) -> None:
                                       ctypes.c_double, _dp, _dp, _i64p, ctypes.POINTER(Cons),
                                       ctypes.POINTER(Motion)], _i32),
         "mac_motion_thresholds": ([ctypes.c_double, ctypes.c_double, _dp, _dp], None),
+        "mac_cons_explain_f64": ([_vp, _dp, _i64, _i64, _dp, _dp, ctypes.c_double, ctypes.POINTER(Cons),
+                                  ctypes.POINTER(Motion), ctypes.POINTER(Verdict)], _i32),
+        "mac_verdict_read": ([_vp, _i64p, _i64p, _i64p, _i64p, _i32], _i32),
         "mac_mads_run_motion": ([_vp, _dp, _i64, _dp, ctypes.c_double, _dp, _dp, ctypes.c_double,
                                  ctypes.POINTER(MadsParams), _dp, ctypes.POINTER(MadsStats),
                                  ctypes.POINTER(Cons), ctypes.POINTER(MadsOpts),
@@ -689,6 +715,25 @@ class Context:
         integer granularities; on by the poll's signed integer draws, which pack at every granularity.
         Results are the same; read when a run or a stepper begins (a stepper keeps its mode)."""
         self.set_option(MAC_OPT_MESH_KEYS, MAC_KEYS_MESH if on else MAC_KEYS_VALUE)
+
+    def set_verdicts(self, on: bool = True) -> None:
+        """Whether the native MADS driver tallies what rejected the candidates of the polls it
+        generates (MAC_OPT_VERDICTS; verdict_read). Read when a run or a stepper begins (a stepper
+        keeps what it began with); results and statistics are the same either way. A run with
+        ``prog=`` ignores it."""
+        self.set_option(MAC_OPT_VERDICTS, 1 if on else 0)
+
+    def verdict_read(self, reset: bool = True) -> dict:
+        """mac_verdict_read: the driver's tally since the last reset, as ``dict(candidates,
+        rejected_any, rejected_by={"cons3": .., "cons8": .., "cons7": .., "cons4": .., "cons5": ..,
+        "cons6": ..}, polls)``. Synchronises the device."""
+        c, a, p = _i64(), _i64(), _i64()
+        by = (_i64 * MAC_VERDICT_KINDS)()
+        _check(self._L.mac_verdict_read(self._h, ctypes.byref(c), ctypes.byref(a), by, ctypes.byref(p),
+                                        1 if reset else 0))
+        return {"candidates": int(c.value), "rejected_any": int(a.value),
+                "rejected_by": {k: int(by[q]) for q, k in enumerate(VERDICT_KINDS)},
+                "polls": int(p.value)}
 
     def set_algo(self, algo: str) -> None:
         if algo not in ALGOS:
@@ -952,6 +997,28 @@ class Context:
                                          ctypes.byref(cs) if cs is not None else None,
                                          out.ctypes.data_as(_u8p)))
         return out[:K].astype(bool)
+
+    def cons_explain(self, cands, cons=None, motion=None, prev=None, d_lim=None,
+                     tan_half_fov: float = 1.0) -> np.ndarray:
+        """mac_cons_explain_f64: what rejects each candidate (K x 3N rows), one VERDICT_DTYPE record
+        each: every constraint that is on (``cons``, ``motion`` as cons_mask takes them; cons3 through
+        ``prev`` / ``d_lim`` / ``tan_half_fov`` as poll_best takes them) is evaluated for every
+        candidate, none short-circuits another. TDM_Constraints.explain is the host mirror. No point
+        list needed."""
+        c = _f64(cands)
+        if c.ndim != 2:
+            raise ValueError("cands must be K x 3N")
+        K, three_n = c.shape
+        out = np.zeros(max(K, 1), dtype=VERDICT_DTYPE)
+        cs = make_cons(cons)
+        mo = make_motion(motion)
+        pv = _f64(prev) if prev is not None else None
+        dl = _f64(d_lim) if d_lim is not None else None
+        _check(self._L.mac_cons_explain_f64(
+            self._h, _ptr(c), three_n, K, _ptr(pv) if pv is not None else None,
+            _ptr(dl) if dl is not None else None, float(tan_half_fov), _opt(cs), _opt(mo),
+            out.ctypes.data_as(ctypes.POINTER(Verdict))))
+        return out[:K]
 
     def prog_h(self, cands, prog) -> np.ndarray:
         """mac_prog_h_f64: the progressive constraints' violation h of each candidate (K x 3N rows)

@@ -44,6 +44,10 @@ struct EvalReq {
     const mac::ConsArgs* cons = nullptr;
     const mac::MotionArgs* motion = nullptr;
     const ProgLaunch* prog = nullptr;
+    // ... and its verdicts (MAC_OPT_VERDICTS; k_cons.h cons_explain_gen_kernel): the constraints that are
+    // on and the context's tally; one more launch behind the prep, read by nothing of the chain
+    const mac::ExplainArgs* explain = nullptr;
+    unsigned long long* d_tally = nullptr;
 };
 
 // What eval_plan reads: the context's options and list facts, the source's kind, the outputs wanted.

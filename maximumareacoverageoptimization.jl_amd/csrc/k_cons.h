@@ -161,6 +161,13 @@ static inline void motion_thresholds(double p, double a, double* qhi, double* ql
     }
 }
 
+// cons7's test of one UAV at (y, r), as the loaders of cons_violates and motion_violates spell it (they
+// keep their own line: a call here compiled cons_mask_kernel to other code); cons_explain's form.
+__device__ __forceinline__ bool zone_rejects(const ConsArgs& a, double y, double r)
+{
+    return a.zone && y < a.zone_y && r > a.zone_r;
+}
+
 // The motion tests of UAV e at (x, y, r) (r is read only under cons5 / cons6).
 __device__ __forceinline__ bool motion_rejects(const MotionArgs& m, int e, int N, double x, double y, double r)
 {
@@ -429,6 +436,303 @@ __global__ __launch_bounds__(kConsBlock) void cons_mask_gen_motion_kernel(uint64
         else
             v = motion_violates<S>(load, N, a, m);
         if (threadIdx.x == 0) feasible[k] = v ? 0 : 1;
+    }
+    ts_end(ts);
+}
+
+// ------------------------------------------------------------------ verdicts (mac_verdict, include/maxcover.h)
+// What rejected a candidate: every constraint that is on is evaluated for every candidate and kept
+// apart per kind, where the masks above stop at the first rejection. Kind q's bit is set exactly when
+// the existing code rejects the candidate under that constraint alone, because the tests are the
+// existing ones: cons3 is the prep launches' pen_term / pen_threshold (k_prep.h), cons7 zone_rejects,
+// cons4 / cons5 / cons6 motion_rejects with one flag on, cons8 the pair predicate of the header under
+// the same sort and the same cull. All outputs are integers (counts and lowest indices), so no order
+// of threads or atomics shows in them.
+//
+// cons8 here counts where cons_violates stops: the sweep runs to the end, whatever the per-UAV tests
+// found. The cull's proof (the header, 1-3) does not depend on stopping early: a pair that is skipped,
+// alone or as the rest of a run from cell c on, is proven feasible, and every other unordered pair of
+// finite UAVs is tested once, from its lower sorted position. So the number of tested pairs that
+// satisfy a <= T is the number of violating pairs exactly, and a UAV is in a violating pair iff one
+// of the tests it took part in (as either end) succeeded. Each sorted position carries its UAV's
+// index (uint16: N <= 2048) and an "in a pair" byte that either end may set to 1: a same-value race
+// in LDS, read after a barrier. Dynamic LDS: 20 * 256 S bytes (x, y, index, cell, byte).
+constexpr int kVerdictKinds = 6;
+enum VerdictKind { kKindCons3 = 0, kKindCons8 = 1, kKindCons7 = 2, kKindCons4 = 3, kKindCons5 = 4, kKindCons6 = 5 };
+constexpr int kVerdictTally = 2 + kVerdictKinds;   // candidates, rejected by any, rejected by kind q
+
+struct Verdict {   // mac_verdict
+    uint32_t reasons;
+    int32_t pairs;
+    int32_t n_uav[kVerdictKinds];
+    int32_t first_uav[kVerdictKinds];
+    int32_t reserved[2];
+};
+static_assert(sizeof(Verdict) == 64, "one 64-byte record per candidate");
+
+struct ExplainArgs {
+    ConsArgs a;      // cons8, cons7
+    MotionArgs m;    // cons4, cons5, cons6 (every flag 0: off, the arrays unread)
+    PenArgs pa;      // cons3: prev (null: off), dlimT, tan_half_fov; rmax null
+};
+
+// One candidate by one workgroup, as cons_violates takes it. Thread 0 writes *out; tally (the
+// generated-poll kernel; null: none) takes one add per non-zero term.
+template <int S, bool SEP, class Load>
+__device__ __forceinline__ void cons_explain(Load load, int N, const ExplainArgs& xa, Verdict* out,
+                                             unsigned long long* tally)
+{
+    static_assert(kConsCells == kConsBlock, "one cell per thread");
+    constexpr int P = kConsBlock * S;
+    constexpr int NW = kConsBlock / kWave;
+    constexpr int kNone = 0x7fffffff;
+    __shared__ int wcnt[NW][kVerdictKinds], wfirst[NW][kVerdictKinds], wpairs[NW];
+    const ConsArgs& a = xa.a;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const double inf = __builtin_inf();
+    // motion_rejects with one constraint on: the kind's own verdict
+    MotionArgs m4 = xa.m, m5 = xa.m, m6 = xa.m;
+    m4.speed = m4.accel = 0;
+    m5.cone = m5.accel = 0;
+    m6.cone = m6.speed = 0;
+    int cnt[kVerdictKinds], first[kVerdictKinds];   // of this wave (uniform)
+#pragma unroll
+    for (int q = 0; q < kVerdictKinds; ++q) {
+        cnt[q] = 0;
+        first[q] = kNone;
+    }
+    double kx[S], ky[S];
+    double lo = inf, hi = -inf;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        const int e = s * kConsBlock + tid;
+        kx[s] = inf;   // +inf: not a UAV of the pair tests (past N, or a non-finite coordinate)
+        ky[s] = 0.0;
+        bool f[kVerdictKinds] = {false, false, false, false, false, false};
+        if (e < N) {
+            double x, y, r;
+            load(e, x, y, r);
+            if (xa.pa.prev) f[kKindCons3] = pen_term(x, y, r, e, N, xa.pa, pen_threshold(xa.pa, e)) < 0.0;
+            f[kKindCons7] = zone_rejects(a, y, r);
+            if (xa.m.cone) f[kKindCons4] = motion_rejects(m4, e, N, x, y, r);
+            if (xa.m.speed) f[kKindCons5] = motion_rejects(m5, e, N, x, y, r);
+            if (xa.m.accel) f[kKindCons6] = motion_rejects(m6, e, N, x, y, r);
+            if (__builtin_fabs(x) < inf && __builtin_fabs(y) < inf) {
+                kx[s] = x;
+                ky[s] = y;
+                lo = x < lo ? x : lo;
+                hi = x > hi ? x : hi;
+            }
+        }
+        // (every lane arrives here; the slots go up in e, so a wave's first hit is its lowest index)
+#pragma unroll
+        for (int q = 0; q < kVerdictKinds; ++q) {
+            if (q == kKindCons8) continue;
+            const uint64_t b = __ballot(f[q]);
+            if (b != 0 && first[q] == kNone) first[q] = s * kConsBlock + wave * kWave + __builtin_ctzll(b);
+            cnt[q] += __popcll(b);
+        }
+    }
+    int pairs = 0;
+    if constexpr (SEP) {
+        extern __shared__ double cons_lds[];
+        double* const sx = cons_lds;
+        double* const sy = cons_lds + P;
+        uint16_t* const si = reinterpret_cast<uint16_t*>(cons_lds + 2 * P);   // the position's UAV
+        unsigned char* const sc = reinterpret_cast<unsigned char*>(si + P);   // its cell
+        unsigned char* const sp = sc + P;                                     // 1: in a violating pair
+        __shared__ double bnd[kConsCells];
+        __shared__ int ccnt[kConsCells];
+        __shared__ int start[kConsCells + 1];
+        __shared__ double wmin[NW], wmax[NW];
+        __shared__ int wsum[NW];
+        ccnt[tid] = 0;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double l2 = __shfl_xor(lo, off, kWave), h2 = __shfl_xor(hi, off, kWave);
+            lo = l2 < lo ? l2 : lo;
+            hi = h2 > hi ? h2 : hi;
+        }
+        if (lane == 0) {
+            wmin[wave] = lo;
+            wmax[wave] = hi;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NW; ++q) {
+            lo = wmin[q] < lo ? wmin[q] : lo;
+            hi = wmax[q] > hi ? wmax[q] : hi;
+        }
+        // the cells of cons_violates: width w >= dcut over [lo, hi], bnd non-decreasing, bnd[0] = lo
+        const double ext = (hi - lo) / (double)kConsCells;
+        const double w = a.dcut > ext ? a.dcut : ext;
+        const double invw = 1.0 / w;
+        bnd[tid] = tid == 0 ? lo : lo + (double)tid * w;
+        __syncthreads();
+        if (a.sep && N > 1 && lo < inf) {   // workgroup-uniform
+            int g[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                g[s] = -1;
+                if (kx[s] < inf) {
+                    const double u = (kx[s] - lo) * invw;
+                    int q = u >= (double)(kConsCells - 1) ? kConsCells - 1 : u > 0.0 ? (int)u : 0;
+                    while (q > 0 && kx[s] < bnd[q]) --q;
+                    while (q < kConsCells - 1 && kx[s] >= bnd[q + 1]) ++q;
+                    g[s] = q;
+                    atomicAdd(&ccnt[q], 1);
+                }
+            }
+            __syncthreads();
+            const int mine = ccnt[tid];
+            int incl = mine;
+#pragma unroll
+            for (int off = 1; off < kWave; off <<= 1) {
+                const int v = __shfl_up(incl, off, kWave);
+                if (lane >= off) incl += v;
+            }
+            if (lane == kWave - 1) wsum[wave] = incl;
+            __syncthreads();
+            int base = 0, total = 0;
+#pragma unroll
+            for (int q = 0; q < NW; ++q) {
+                base += q < wave ? wsum[q] : 0;
+                total += wsum[q];
+            }
+            start[tid] = base + incl - mine;
+            ccnt[tid] = base + incl - mine;   // the cell's fill cursor
+            if (tid == 0) start[kConsCells] = total;
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (g[s] >= 0) {
+                    const int pos = atomicAdd(&ccnt[g[s]], 1);
+                    sx[pos] = kx[s];
+                    sy[pos] = ky[s];
+                    si[pos] = (uint16_t)(s * kConsBlock + tid);
+                    sc[pos] = (unsigned char)g[s];
+                    sp[pos] = 0;
+                }
+            }
+            __syncthreads();
+            const int nv = start[kConsCells];
+            // the sweep of cons_violates, to the end: every tested pair that violates is counted once
+            for (int p = tid; p < nv; p += kConsBlock) {
+                const double xi = sx[p], yi = sy[p];
+                int cell = sc[p];
+                bool hit = false;
+                for (int q = p + 1; q < nv; ++q) {
+                    const int cq = sc[q];
+                    if (cq != cell) {   // a later cell: everything from here on has x >= bnd[cq]
+                        if (bnd[cq] - xi >= a.dcut) break;
+                        cell = cq;
+                    }
+                    const double dx = sx[q] - xi;
+                    if (__builtin_fabs(dx) >= a.dcut) continue;
+                    const double dy = sy[q] - yi;
+                    if (dx * dx + dy * dy <= a.T) {
+                        ++pairs;
+                        hit = true;
+                        sp[q] = 1;
+                    }
+                }
+                if (hit) sp[p] = 1;
+            }
+            __syncthreads();   // (the bytes, whichever end set them)
+            int c8 = 0, f8 = kNone;
+            for (int p = tid; p < nv; p += kConsBlock) {
+                if (sp[p]) {
+                    const int e = si[p];
+                    ++c8;
+                    f8 = e < f8 ? e : f8;
+                }
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                pairs += __shfl_xor(pairs, off, kWave);
+                c8 += __shfl_xor(c8, off, kWave);
+                const int o = __shfl_xor(f8, off, kWave);
+                f8 = o < f8 ? o : f8;
+            }
+            cnt[kKindCons8] = c8;
+            first[kKindCons8] = f8;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < kVerdictKinds; ++q) {
+            wcnt[wave][q] = cnt[q];
+            wfirst[wave][q] = first[q];
+        }
+        wpairs[wave] = pairs;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        Verdict v;
+        v.reasons = 0u;
+        v.pairs = 0;
+#pragma unroll
+        for (int q = 0; q < kVerdictKinds; ++q) {
+            int c = 0, fi = kNone;
+#pragma unroll
+            for (int wv = 0; wv < NW; ++wv) {
+                c += wcnt[wv][q];
+                fi = wfirst[wv][q] < fi ? wfirst[wv][q] : fi;
+            }
+            v.n_uav[q] = c;
+            v.first_uav[q] = c ? fi : -1;
+            v.reasons |= c ? 1u << q : 0u;
+        }
+#pragma unroll
+        for (int wv = 0; wv < NW; ++wv) v.pairs += wpairs[wv];
+        v.reserved[0] = v.reserved[1] = 0;
+        *out = v;
+        if (tally) {   // integer adds: the totals are the same in any order
+            atomicAdd(&tally[0], 1ull);
+            if (v.reasons) atomicAdd(&tally[1], 1ull);
+#pragma unroll
+            for (int q = 0; q < kVerdictKinds; ++q)
+                if (v.reasons >> q & 1u) atomicAdd(&tally[2 + q], 1ull);
+        }
+    }
+}
+
+// Workgroup = candidate (column k of the 3N x K matrix). SEP: cons8 is on (the sort and its dynamic LDS).
+template <int S, bool SEP>
+__global__ __launch_bounds__(kConsBlock) void cons_explain_kernel(const double* __restrict__ cands, int N,
+                                                                ExplainArgs xa, Verdict* __restrict__ out)
+{
+    const double* __restrict__ c = cands + (size_t)blockIdx.x * (size_t)(3 * N);
+    cons_explain<S, SEP>(
+        [&](int e, double& x, double& y, double& r) {
+            x = c[e];
+            y = c[N + e];
+            r = c[2 * N + e];
+        },
+        N, xa, out + blockIdx.x, nullptr);
+}
+
+// The verdicts of a generated poll (the native MADS driver under MAC_OPT_VERDICTS): workgroup =
+// candidate k of the source, drawn as cons_mask_gen_motion_kernel draws it; the record into the
+// launch's own scratch and the context's tally. Enqueued behind the poll's prep launch: in the
+// pipelined loop the launch returns (uniform per workgroup, before any barrier) once the loop has
+// stopped or when the prep rejected the poll whole, and tallies nothing then.
+template <int S, bool SEP>
+__global__ __launch_bounds__(kConsBlock) void cons_explain_gen_kernel(uint64_t* ts, CandSrc src, int N,
+                                                                    ExplainArgs xa, Verdict* __restrict__ out,
+                                                                    unsigned long long* tally)
+{
+    ts_begin(ts);   // profiling only (k_common.h); the driver passes null
+    if (src.resolve()) {
+        const int k = (int)blockIdx.x;
+        const bool need_r = xa.a.zone | xa.m.speed | xa.m.accel | (xa.pa.prev != nullptr);
+        cons_explain<S, SEP>(
+            [&](int e, double& x, double& y, double& r) {
+                x = src.get(k, e, N);
+                y = src.get(k, N + e, N);
+                r = need_r ? src.get(k, 2 * N + e, N) : 0.0;
+            },
+            N, xa, out + k, tally);
     }
     ts_end(ts);
 }

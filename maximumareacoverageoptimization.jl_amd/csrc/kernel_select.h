@@ -46,6 +46,22 @@ static MaskGenMotionKern mask_gen_motion_kern(int S, bool sep)
 // the sort's LDS of a mask launch: x, y, cell per sorted position
 static uint32_t mask_lds(int S) { return (uint32_t)(17 * kConsBlock * S); }
 
+// the verdict launches (k_cons.h cons_explain): sep selects the build with the sort; its LDS adds each
+// position's UAV index (2 B) and its "in a pair" byte
+using ExplainKern = void (*)(const double*, int, ExplainArgs, Verdict*);
+using ExplainGenKern = void (*)(uint64_t*, CandSrc, int, ExplainArgs, Verdict*, unsigned long long*);
+static ExplainKern explain_kern(int S, bool sep)
+{
+    return sep ? by_slots(S, [](auto v) -> ExplainKern { return cons_explain_kernel<decltype(v)::value, true>; })
+               : by_slots(S, [](auto v) -> ExplainKern { return cons_explain_kernel<decltype(v)::value, false>; });
+}
+static ExplainGenKern explain_gen_kern(int S, bool sep)
+{
+    return sep ? by_slots(S, [](auto v) -> ExplainGenKern { return cons_explain_gen_kernel<decltype(v)::value, true>; })
+               : by_slots(S, [](auto v) -> ExplainGenKern { return cons_explain_gen_kernel<decltype(v)::value, false>; });
+}
+static uint32_t explain_lds(int S, bool sep) { return sep ? (uint32_t)(20 * kConsBlock * S) : 0u; }
+
 // (a mesh belongs to a generated poll: prep_x_kernel's matrix build has none)
 using PrepKern = void (*)(uint64_t*, PrepArgs);
 // (mesh: EvalPlan.mesh, the kMesh argument: 0 none, 1 a mesh with value keys, kMeshKeys)

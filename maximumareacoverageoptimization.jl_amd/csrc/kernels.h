@@ -31,6 +31,10 @@
 //   cons_mask_kernel      the swarm constraints (minimum spacing cons8, altitude zone cons7), one
 //                         feasibility byte per candidate: UAVs counting-sorted by x into cells in LDS,
 //                         pairs tested up to the spacing apart; cons_argmin_kernel: the masked poll's argmin (k_cons.h)
+//   cons_explain_kernel   what rejected each candidate (mac_verdict): every constraint that is on, kept apart
+//                         per kind (UAV counts, lowest index, cons8's pair count from the same sort swept to
+//                         the end); cons_explain_gen_kernel: the same over a generated poll, into the
+//                         context's tally (k_cons.h)
 //   prog_h_kernel         the progressive constraints' violation h per candidate (altitude excess folded
 //                         per constraint in UAV order); prog_select_kernel: the progressive barrier's
 //                         update over an iteration's polls, one 64-byte record (k_prog.h)

@@ -52,6 +52,10 @@ struct mac_mads {
     int64_t slot_fallbacks = 0;   // slot waits that timed out (copy + sync instead)
     int route_five = 0;           // the polls are crowded (host_crowded_disks at begin): five-launch chain
     int mesh_keys = 0;            // the run keys its polls in mesh units (MAC_OPT_MESH_KEYS as it began, on a mesh)
+    // verdicts (MAC_OPT_VERDICTS as the stepper began, with cons3 or a swarm or motion constraint on, no
+    // mac_prog): every generated poll's explain launch (k_cons.h) and the context's tally it adds to
+    ExplainArgs explain{};
+    unsigned long long* d_tally = nullptr;   // null: off
     double* ext_best = nullptr;   // mac_mads_best_buffer: the polls' best goes here
     // the mesh (mac_mads_begin_mesh): the granularity of every variable, host copy and device copy
     // (empty / null: 1.0 everywhere, the calls without a mesh)
@@ -205,6 +209,10 @@ static EvalReq mads_request(mac_mads* m, const CandSrc& src, int Kc)
     rq.d_best = mads_best_ptr(m);
     rq.cons = m->has_cons ? &m->cons : nullptr;
     rq.motion = m->has_mot ? &m->mot : nullptr;
+    if (m->d_tally) {
+        rq.explain = &m->explain;
+        rq.d_tally = m->d_tally;
+    }
     return rq;
 }
 
@@ -251,6 +259,12 @@ static void mads_wait_best(mac_mads* m, double* obj, int64_t* idx, uint64_t* fea
     }
 }
 
+// A poll's explain launch was enqueued with it (mads_request): one tallied launch.
+static void mads_count_verdict_poll(mac_mads* m, int64_t polls = 1)
+{
+    if (m->d_tally && polls > 0) m->ctx->verdict_polls.fetch_add(polls, std::memory_order_relaxed);
+}
+
 // The stepper's shard of the poll at (state, b) around its incumbent, with the permutations (rp, cp),
 // enqueued through the slot. The lane's staging is free: the previous poll's copy preceded its
 // finalize, whose results were read.
@@ -261,6 +275,7 @@ static void mads_enqueue_poll(mac_mads* m, uint64_t state, int64_t b, const std:
     const int* d_perm = mads_stage(m, m->x.data(), rp, cp, m->hx, m->L->xinc.p);
     mads_best_of(m, mads_gen_src(m, m->L->xinc.as<double>(), d_perm, state, b, (int)m->lo), (int)(m->hi - m->lo),
                  m->lo, true);
+    mads_count_verdict_poll(m);
 }
 
 static void mads_free(mac_mads* m)
@@ -315,6 +330,8 @@ struct MadsSetup {
     const mac_mads_mesh* mesh = nullptr;
     bool checked = false, xy = false;
     const double* gran = nullptr;
+    bool prog = false;   // a mac_prog run or stepper: MAC_OPT_VERDICTS is ignored (nothing allocated, no check)
+    bool verdicts = false;   // MAC_OPT_VERDICTS as the run begins (read once: mads_begin_impl), false under prog
 };
 
 static int32_t mads_setup_check(MadsSetup& su, int64_t three_n)
@@ -359,6 +376,10 @@ static int32_t mads_begin_check(mac_ctx* ctx, const double* x0, int64_t three_n,
     if (sh.has_cons && sh.N > kConsMaxN)
         return fail(MAC_E_INVAL, "mac_mads_begin_cons: N = " + std::to_string(sh.N) + " > " +
                                      std::to_string(kConsMaxN) + " UAVs under a swarm constraint");
+    // the verdict launch sorts as the mask does: with the option on, cons3 alone meets the same limit
+    if (su.verdicts && (sh.has_cons || prev) && sh.N > kConsMaxN)
+        return fail(MAC_E_INVAL, "MAC_OPT_VERDICTS: N = " + std::to_string(sh.N) + " > " + std::to_string(kConsMaxN) +
+                                     " UAVs under a constraint (the verdict kernel's limit)");
     return MAC_OK;
 }
 
@@ -448,6 +469,17 @@ static void mads_begin_route(mac_mads* m)
     m->route_five = mads_route_five(m->route_five != 0, m->g.empty() ? nullptr : m->g.data(), np, m->mesh_keys != 0);
 }
 
+// MAC_OPT_VERDICTS as the run begins (like mesh_keys: the stepper keeps it): with a constraint on, the
+// explain launch's arguments from the stepper's own uploads and the context's tally.
+static void mads_begin_verdicts(mac_mads* m, bool on)
+{
+    if (!on || !(m->has_cons || m->d_prev)) return;
+    ConsArgs a = m->cons;
+    if (!(a.sep || a.zone)) a = cons_args(0.0, NAN, NAN);   // (a motion constraint or cons3 alone)
+    m->explain = explain_args(a, m->has_mot ? &m->mot : nullptr, m->d_prev, m->d_dlimT, m->tan_half_fov);
+    m->d_tally = verdict_tally(m->ctx);
+}
+
 // The stream's seed and the first iteration's permutations. They do not depend on the poll outcomes:
 // the next iteration's are computed on the host while the device evaluates the current poll.
 static void mads_begin_stream(mac_mads* m)
@@ -466,6 +498,8 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
     *out = nullptr;
     int32_t rc = mads_setup_check(su, three_n);
     if (rc) return rc;
+    // (the option is read once: the size check below and the tally follow the same value)
+    su.verdicts = ctx && !su.prog && ctx->verdicts.load(std::memory_order_relaxed) != 0;
     MadsShape sh;
     rc = mads_begin_check(ctx, x0, three_n, r_max, prev, d_lim, prm, shard_lo, shard_hi, su, sh);
     if (rc) return rc;
@@ -494,6 +528,7 @@ static int32_t mads_begin_impl(mac_ctx* ctx, const double* x0, int64_t three_n, 
         m->ell = prm->ell0;
         mads_begin_route(m);
         mads_begin_stream(m);
+        mads_begin_verdicts(m, su.verdicts);
     } catch (...) {
         mads_free(m);
         throw;
@@ -811,6 +846,7 @@ static void mads_run_pipelined(mac_mads* m)
     m->evals = 1 + st.it * (int64_t)m->K;
     m->rejected += st.skipped;
     m->succ += st.succ;
+    mads_count_verdict_poll(m, st.it - st.skipped);   // (the launches past the stop and of skipped polls returned)
     if (st.feas) {   // (the stepper's counter holds the polls' evaluations: none before this loop)
         const unsigned long long fe = st.feas;
         HCK(hipMemcpy(m->d_feas.p, &fe, sizeof(fe), hipMemcpyHostToDevice));
@@ -1092,6 +1128,7 @@ int32_t mac_mads_run_prog(mac_ctx* ctx, const double* x0, int64_t three_n, const
         return fail(MAC_E_INVAL, "mac_prog: h(x0) = " + std::to_string(h0) + " > h_max0 = " + std::to_string(h_max));
     rc = mads_setup_check(su, three_n);
     if (rc) return rc;
+    su.prog = true;   // (MAC_OPT_VERDICTS is ignored)
     mac_mads* m = nullptr;
     rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, 0,
                          mads_poll_count(three_n, su.xy), &m, su);
@@ -1143,6 +1180,7 @@ int32_t mac_mads_begin_prog(mac_ctx* ctx, const double* x0, int64_t three_n, con
         return fail(MAC_E_INVAL, "mac_prog: h(x0) = " + std::to_string(h0) + " > h_max0 = " + std::to_string(h_max));
     rc = mads_setup_check(su, three_n);
     if (rc) return rc;
+    su.prog = true;   // (MAC_OPT_VERDICTS is ignored)
     mac_mads* m = nullptr;
     rc = mads_begin_impl(ctx, x0, three_n, r_max, penalty, prev, d_lim, tan_half_fov, prm, shard_lo, shard_hi, &m, su);
     if (rc) return rc;

@@ -179,6 +179,7 @@ struct Lane {
     DevBuf bdpart, bdarrive, bdout;            // by_disk_kernel: owned words, arrivals; host calls' results
     DevBuf cmask, cbest;                       // masked poll (k_cons.h): feasibility bytes; the chain's own best
     DevBuf motion;                             // mac_motion's per-UAV arrays (k_cons.h MotionArgs): 8N doubles
+    DevBuf verdict;                            // verdict records (k_cons.h Verdict): 64 B per candidate
     DevBuf prog, progh, progobj, progrec;      // mac_prog (k_prog.h): member and limit; h and the first centre's
                                                // objectives of an iteration; prog_select_kernel's record
     std::vector<double> h_motion;              // ... as built on the host
@@ -275,6 +276,12 @@ struct mac_ctx {
     int shared_mode = MAC_SHARED_AUTO;   // MAC_OPT_SHARED
     int chain = MAC_CHAIN_AUTO;          // MAC_OPT_CHAIN
     int mesh_keys = MAC_KEYS_VALUE;      // MAC_OPT_MESH_KEYS (read when a MADS run or stepper begins)
+    // MAC_OPT_VERDICTS (read when a MADS run or stepper begins): the tally the generated polls' explain
+    // launches add to (k_cons.h kVerdictTally words; allocated by the first stepper that needs it, under
+    // mu) and the launches tallied (counted on the host: mac_verdict_read)
+    std::atomic<int> verdicts{0};
+    DevBuf vtally;
+    std::atomic<int64_t> verdict_polls{0};
     bool profile = false;
     // In-kernel launch timing (k_common.h ts_begin / ts_end): each profiled walk launch takes
     // nwg consecutive {start, end} slots of `stamps`. a: the scan / tiled launch, b: the poll
@@ -762,6 +769,23 @@ static void enqueue_gen_masks(EvalRun& r)
     r.d_mask8 = d_mask;
 }
 
+// A generated poll's verdicts (MAC_OPT_VERDICTS; k_cons.h cons_explain_gen_kernel): one launch behind the
+// poll's prep launch, so that in the pipelined loop it sees the prep's whole-poll rejection and returns
+// as the chain's later launches do. It writes the lane's record scratch and the context's tally; nothing
+// of the chain reads either. No profile role, no stamps.
+static void enqueue_explain(EvalRun& r)
+{
+    const EvalReq& rq = r.rq;
+    if (!rq.explain || !rq.d_tally || rq.src.cands || rq.K <= 0) return;
+    const int N = rq.N, K = rq.K;
+    const int S = cons_slots(N);   // (N <= kConsMaxN: mads_begin_check, also under cons3 alone)
+    const bool sep = rq.explain->a.sep != 0;
+    r.L->verdict.reserve(sizeof(Verdict) * (size_t)K);
+    hipLaunchKernelGGL(explain_gen_kern(S, sep), dim3((unsigned)K), dim3(kConsBlock), explain_lds(S, sep), r.s,
+                       (uint64_t*)nullptr, rq.src, N, *rq.explain, r.L->verdict.as<Verdict>(), rq.d_tally);
+    HCK(hipGetLastError());
+}
+
 // The fused chain's turn under AUTO: the lane's last poll's report goes into the context's history,
 // and the chain runs unless one of the last 64 reported polls did not suit it: a crowded poll (many
 // shared entries: the five-launch chain's union pass), a scattered batch (the per-candidate walk) or
@@ -890,6 +914,7 @@ static void enqueue_fused(EvalRun& r)
     hipLaunchKernelGGL(prep_kern(pl.prep_fused, pl.mesh), dim3((unsigned)pl.nprep), prep_block(pl.prep_fused), 0, s,
                        tsk, pr);
     HCK(hipGetLastError());
+    enqueue_explain(r);
     if (ctx->host_stats) h2 = hclk::now();
     fa.N = N;
     fa.K = K;
@@ -1009,6 +1034,7 @@ static void enqueue_prep_five(EvalRun& r, CandSrc& keyed)
     hipLaunchKernelGGL(prep_kern(pl.prep_five, pl.mesh), dim3((unsigned)pl.nrec), prep_block(pl.prep_five), 0, r.s,
                        tsk, pr);
     HCK(hipGetLastError());
+    enqueue_explain(r);
 }
 
 // The shared entries of crowded polls: the union pass (equal weights, k_or.h) or bit-words per
@@ -2228,7 +2254,7 @@ void mac_ctx_destroy(mac_ctx* ctx)
                           &l->cpart, &l->carrive, &l->ctot, &l->clv, &l->prec, &l->cost, &l->nboxU,
                           &l->ncountU, &l->orjobs, &l->pd, &l->dead8, &l->frows, &l->fwhint, &l->fwlist, &l->fwcount,
                           &l->fwsxy, &l->fwsw, &l->bdpart, &l->bdarrive, &l->bdout, &l->cmask, &l->cbest,
-                          &l->motion, &l->prog, &l->progh, &l->progobj, &l->progrec})
+                          &l->motion, &l->verdict, &l->prog, &l->progh, &l->progobj, &l->progrec})
             b->release();
         if (l->done) (void)hipEventDestroy(l->done);
 
@@ -2239,7 +2265,7 @@ void mac_ctx_destroy(mac_ctx* ctx)
                       &ctx->keys_in, &ctx->keys_out, &ctx->idx_in, &ctx->tmp, &ctx->bbox,
                       &ctx->flags_s, &ctx->flags_o, &ctx->keep, &ctx->sel_count, &ctx->cx,
                       &ctx->cy, &ctx->cw, &ctx->cidx, &ctx->circ, &ctx->cdisk, &ctx->rboxes,
-                      &ctx->rcount, &ctx->ritems, &ctx->rpart, &ctx->rout})
+                      &ctx->rcount, &ctx->ritems, &ctx->rpart, &ctx->rout, &ctx->vtally})
         b->release();
     ctx->stamps.release();
     if (ctx->setup_stream) (void)hipStreamDestroy(ctx->setup_stream);
@@ -2290,6 +2316,10 @@ int32_t mac_set_option(mac_ctx* ctx, int32_t option, int64_t value)
     case MAC_OPT_MESH_KEYS:
         if (value != MAC_KEYS_VALUE && value != MAC_KEYS_MESH) return fail(MAC_E_INVAL, "bad mesh keys mode");
         ctx->mesh_keys = (int)value;
+        return MAC_OK;
+    case MAC_OPT_VERDICTS:
+        if (value != 0 && value != 1) return fail(MAC_E_INVAL, "bad verdicts mode");
+        ctx->verdicts.store((int)value, std::memory_order_relaxed);
         return MAC_OK;
     case MAC_OPT_TILE_POINTS:
         if (value < 1 || value > 4096) return fail(MAC_E_INVAL, "tile points out of range");
@@ -3855,6 +3885,123 @@ int32_t mac_poll_best_motion_f64(mac_ctx* ctx, const double* cands, int64_t thre
     cons_active(cons, &a);
     return host_eval<double>(ctx, cands, three_n, K, r_max, penalty, prev, d_lim, tan_half_fov, nullptr,
                              obj_out, best_obj, best_idx, &a, motion);
+    ABI_END
+}
+
+// ---- constraint verdicts (k_cons.h cons_explain; include/maxcover.h mac_verdict)
+
+static_assert(sizeof(mac_verdict) == sizeof(Verdict) && MAC_VERDICT_KINDS == kVerdictKinds, "mac_verdict is Verdict");
+
+// The explain launches' arguments from what a call or a stepper has on: the swarm constraints (a: all
+// off when none), the motion arrays as uploaded (null: none) and cons3's device inputs (null: off).
+static ExplainArgs explain_args(const ConsArgs& a, const MotionArgs* mot, const double* d_prev,
+                                const double* d_dlimT, double tan_half_fov)
+{
+    ExplainArgs xa{};
+    xa.a = a;
+    if (mot) xa.m = *mot;
+    xa.pa = PenArgs{nullptr, d_prev, d_dlimT, nullptr, tan_half_fov};
+    return xa;
+}
+
+int32_t mac_cons_explain_f64(mac_ctx* ctx, const double* cands, int64_t three_n, int64_t K, const double* prev,
+                             const double* d_lim, double tan_half_fov, const mac_cons* cons,
+                             const mac_motion* motion, mac_verdict* out)
+{
+    ABI_BEGIN
+    int32_t rc = cons_check(ctx, cands, three_n, K, out);
+    if (rc) return rc;
+    if (prev && !d_lim) return fail(MAC_E_INVAL, "prev given without d_lim");
+    if (K == 0) return MAC_OK;
+    ConsArgs a{};
+    const bool has_cons = cons_active(cons, &a);
+    if (!has_cons) a = cons_args(0.0, NAN, NAN);   // (everything off, T and dcut defined)
+    bool mc, ms, ma;
+    const bool has_mot = motion_on(motion, &mc, &ms, &ma);
+    if (three_n == 0 || (!has_cons && !has_mot && !prev)) {   // no UAV, or nothing on: nothing rejects
+        for (int64_t k = 0; k < K; ++k) {
+            std::memset(&out[k], 0, sizeof(mac_verdict));
+            for (int q = 0; q < MAC_VERDICT_KINDS; ++q) out[k].first_uav[q] = -1;
+        }
+        return MAC_OK;
+    }
+    const int N = (int)(three_n / 3);
+    set_device(ctx);
+    LaneGuard lg(ctx);
+    Lane* L = lg.lane;
+    hipStream_t s = L->stream;
+    const size_t in_bytes = sizeof(double) * (size_t)three_n * (size_t)K;
+    const size_t out_bytes = sizeof(Verdict) * (size_t)K;
+    L->cands.reserve(in_bytes);
+    L->verdict.reserve(out_bytes);
+    MotionArgs mot{};
+    if (has_mot) mot = motion_upload(L, s, N, motion);
+    if (prev) cons3_upload(L, s, N, prev, d_lim);
+    const ExplainArgs xa = explain_args(a, has_mot ? &mot : nullptr, prev ? L->prev.as<double>() : nullptr,
+                                        prev ? L->dlim.as<double>() : nullptr, tan_half_fov);
+    const bool staged = in_bytes <= ((size_t)64 << 20);
+    if (staged) {
+        L->h_io.reserve(std::max<size_t>(in_bytes, 64));
+        staged_upload(cands, L->h_io.p, L->cands.p, in_bytes, s);
+    } else {
+        HCK(hipMemcpyAsync(L->cands.p, cands, in_bytes, hipMemcpyHostToDevice, s));
+    }
+    constexpr int64_t kMaxWG = (int64_t)1 << 23;   // workgroups per launch (2^31 threads)
+    const int S = cons_slots(N);
+    const bool sep = a.sep != 0;
+    for (int64_t k0 = 0; k0 < K; k0 += kMaxWG) {
+        const int64_t B = std::min(kMaxWG, K - k0);
+        hipLaunchKernelGGL(explain_kern(S, sep), dim3((unsigned)B), dim3(kConsBlock), explain_lds(S, sep), s,
+                           L->cands.as<double>() + (size_t)k0 * (size_t)three_n, N, xa, L->verdict.as<Verdict>() + k0);
+        HCK(hipGetLastError());
+    }
+    // (pageable destination: the copy stages through the runtime and has landed at the synchronisation)
+    HCK(hipMemcpyAsync(out, L->verdict.p, out_bytes, hipMemcpyDeviceToHost, s));
+    HCK(hipStreamSynchronize(s));
+    return MAC_OK;
+    ABI_END
+}
+
+// The context's tally for a stepper that begins with MAC_OPT_VERDICTS on: allocated and zeroed once.
+static unsigned long long* verdict_tally(mac_ctx* ctx)
+{
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->vtally.p) {
+        ctx->vtally.reserve(sizeof(unsigned long long) * kVerdictTally);
+        // (complete before any lane's launch adds to it: the lanes' streams do not wait for the null stream)
+        HCK(hipMemsetAsync(ctx->vtally.p, 0, sizeof(unsigned long long) * kVerdictTally, nullptr));
+        HCK(hipStreamSynchronize(nullptr));
+    }
+    return ctx->vtally.as<unsigned long long>();
+}
+
+int32_t mac_verdict_read(mac_ctx* ctx, int64_t* candidates, int64_t* rejected_any, int64_t* rejected_by,
+                         int64_t* polls, int32_t reset)
+{
+    ABI_BEGIN
+    if (!ctx) return fail(MAC_E_INVAL, "null context");
+    unsigned long long t[kVerdictTally] = {};
+    void* d = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        d = ctx->vtally.p;
+    }
+    if (d) {   // (never allocated: no stepper began with the option on; zeros, no device call)
+        set_device(ctx);
+        HCK(hipDeviceSynchronize());
+        HCK(hipMemcpy(t, d, sizeof(t), hipMemcpyDeviceToHost));
+        if (reset) {   // (complete before the call returns, so before the next launch that adds to it)
+            HCK(hipMemsetAsync(d, 0, sizeof(t), nullptr));
+            HCK(hipStreamSynchronize(nullptr));
+        }
+    }
+    if (candidates) *candidates = (int64_t)t[0];
+    if (rejected_any) *rejected_any = (int64_t)t[1];
+    if (rejected_by)
+        for (int q = 0; q < kVerdictKinds; ++q) rejected_by[q] = (int64_t)t[2 + q];
+    const int64_t np = reset ? ctx->verdict_polls.exchange(0) : ctx->verdict_polls.load();
+    if (polls) *polls = np;
+    return MAC_OK;
     ABI_END
 }
 
